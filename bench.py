@@ -12,7 +12,10 @@ A "step" is one pass of the hot path over the resident batch:
   --threshold > 0), counts written to HBM.  Query text and index are resident in
   HBM before the timed region; nothing is copied to the host inside it.
 
-Usage:  python bench.py --gpus N --steps K --warmup W
+Usage:  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds what the headline does not need:
+the CPU baseline, the end-to-end calls, the cache-cold and HBM-side probes, the self-checks against the oracle and
+the sharded product call.  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy.
 N > 1 = one rank per GPU over RCCL.  Launched by torch.distributed.run (WORLD_SIZE / RANK in the
 environment) the script is one rank of N; started plainly (`python bench.py --gpus 8`) it launches
 the N ranks itself (`launch_plan`): the same torch.distributed.run command, rendezvous on 127.0.0.1.
@@ -702,6 +705,63 @@ def timed(step, steps, warmup, world, backend, after_warmup=None):
     return dt
 
 
+DUMP_PART_BYTES = 24 << 20      # --dump-outputs: at most this many bytes of sampled count rows, and as many of hit records
+DUMP_SEED = 20241016
+
+
+def dump_outputs(path, args, batch, run):
+    """--dump-outputs: what the last timed step left for a caller of the timed path, as float32 / float64 .npy files
+    (< 64 MB in all).  The queries are the same from run to run, so two builds can be compared file by file.
+      count_sums.npy     [m, 3] float64: (query, sum, slot-weighted sum) of every count row this rank holds
+      count_rows.npy     [n, total_counts] float32: a fixed, seeded sample of those rows, element by element
+      count_rows_query.npy [n] float64: the query of each sampled row
+      hits.npy           [h, 4] float64: (query, file, doc, score) of the hit lists of a seeded sample of queries
+                         (thresholded or top-k steps only)
+    Weights of the slot-weighted sum: (slot % 1021) + 1, as the self-check of the sharded line."""
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    if run is not None:
+        # sharded: the rows this rank owns after the exchange (global document order), per sub-batch
+        parts, q_start = [], 0
+        for i in range(len(run.sub)):
+            q0, qn, rows = run.owned_rows(i)
+            parts.append((q_start + q0, qn, rows))
+            q_start += len(run.sub_queries[i])
+    elif (args.hits_only and args.threshold > 0) or (args.num_results > 0 and not args.topk_with_rows):
+        parts = []                          # (the step keeps no score rows)
+    else:
+        parts = [(0, batch.nq, batch.counts_tensor())]
+    parts = [p for p in parts if p[1] > 0]
+    if parts:
+        ncols = parts[0][2].shape[1]
+        w = (torch.arange(ncols, device=parts[0][2].device, dtype=torch.int64) % 1021) + 1
+        sums = []
+        for q0, qn, rows in parts:
+            a, b = _row_sums(rows, w)
+            q = np.arange(q0, q0 + qn, dtype=np.float64)
+            sums.append(np.stack([q, a.cpu().numpy().astype(np.float64), b.cpu().numpy().astype(np.float64)], axis=1))
+        np.save(os.path.join(path, "count_sums.npy"), np.concatenate(sums))
+        owned = sum(qn for _, qn, _ in parts)
+        n = max(1, min(64, owned, DUMP_PART_BYTES // (4 * max(ncols, 1))))
+        pick = np.sort(rng.choice(owned, size=n, replace=False))
+        rows_out, query_out, base = [], [], 0
+        for q0, qn, rows in parts:
+            local = pick[(pick >= base) & (pick < base + qn)] - base
+            if len(local):
+                idx = torch.as_tensor(local, dtype=torch.int64, device=rows.device)
+                rows_out.append(_as_int64(rows.index_select(0, idx)).to(torch.float32).cpu().numpy())
+                query_out.append((local + q0).astype(np.float64))
+            base += qn
+        np.save(os.path.join(path, "count_rows.npy"), np.concatenate(rows_out))
+        np.save(os.path.join(path, "count_rows_query.npy"), np.concatenate(query_out))
+    if run is None and (args.threshold > 0 or args.num_results > 0):
+        nq = batch.nq
+        pick = np.sort(rng.choice(nq, size=min(16, nq), replace=False)) if nq else []
+        recs = [(float(q), float(f), float(d), float(sc)) for q in pick for (f, d, sc) in batch.hits_host(int(q), args.num_results)]
+        hits = np.asarray(recs, dtype=np.float64).reshape(-1, 4)[:DUMP_PART_BYTES // 32]
+        np.save(os.path.join(path, "hits.npy"), hits)
+
+
 def all_ranks_ok(ok, backend):
     """every rank must agree that its set-up succeeded before the next collective, so that a
     local failure (out of memory, ...) cannot strand the others inside RCCL"""
@@ -914,9 +974,17 @@ def main():
                     help="test hook: several ranks on one GPU with --dist-backend nccl -- real RCCL refuses that, which is how the "
                          "preflight's fallback chain is exercised on a one-GPU box")
     ap.add_argument("--test-hang-rank", type=int, default=-1, help=argparse.SUPPRESS)       # test hook of the watchdog: this rank stops stepping
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure and check what it does not need: the CPU baseline, the end-to-end "
+                         "calls, the cache-cold and HBM-side probes, the self-checks against the oracle and the sharded "
+                         "product call.  Off by default: a plain run only sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (rank 0; see dump_outputs)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
 
     launched = "WORLD_SIZE" in os.environ
     if args.dry_run_launch:
@@ -1102,6 +1170,9 @@ def run_bench(args, world, rank, local_rank, wd, emit):
         ms = batch.kernel_ms()                     # HIP events on the launch stream, averaged over the timed steps
         scan_ms, hash_ms, algo = ms["scan_ms"], ms["hash_ms"], batch.stats()["algorithmic_bytes"]
     nlaunch = batch.stats()["scan_launches"] if run is None else sum(b.stats()["scan_launches"] for b in run.sub)
+    if args.dump_outputs and rank == 0:
+        wd.phase("writing the outputs (--dump-outputs)", 300)
+        dump_outputs(args.dump_outputs, args, batch, run)
 
     # whole job: sharded index -> one batch on all ranks; replicated index -> N independent batches
     total_queries = args.queries * (1 if shard_index or world == 1 else world)
@@ -1195,7 +1266,7 @@ def run_bench(args, world, rank, local_rank, wd, emit):
         out["roofline"]["unique_bytes_is"] = ("sum_p row_bytes * S_p * (1 - exp(-Q*T*H/S_p)) distinct rows + the scores written: what must "
                                               "cross the HBM pins at least once per launch (lower bound of the pin traffic; achieved / "
                                               "frac above are algorithmic bytes, every look-up counted)")
-        if world == 1 and not shard_index and not args.no_cpu_baseline:
+        if args.full and world == 1 and not shard_index and not args.no_cpu_baseline:
             out["roofline"]["cache_cold"] = cache_cold_probe(s, cfg, queries, args.kmers, row_bytes)
     if preflight is not None:
         out["preflight"] = preflight
@@ -1220,14 +1291,15 @@ def run_bench(args, world, rank, local_rank, wd, emit):
                            "hidden_frac": round(min(hidden), 4), "hidden_frac_per_rank": [round(h, 4) for h in hidden],
                            "hidden_frac_is": "(scan + hash + exchange ms of a rank - ms_per_step) / (hash + exchange ms), clamped to [0, 1]; min over ranks",
                            "transport": "RCCL in libcobs_gpu.so" if comm is not None else "torch.distributed/" + args.dist_backend}
-        # the line proves itself: exchanged rows against the shards' slices (all rows) and against the oracle (sample)
-        wd.phase("self-check of the exchanged rows", 300)
-        out.update(verify_sharded(run, cfg, world, rank, args.dist_backend, corrupt=args.corrupt_exchange))
+        # --full: the line proves itself: exchanged rows against the shards' slices (all rows) and against the oracle (sample)
+        if args.full:
+            wd.phase("self-check of the exchanged rows", 300)
+            out.update(verify_sharded(run, cfg, world, rank, args.dist_backend, corrupt=args.corrupt_exchange))
         info = s.info(0)
         out["shard_rank0"] = {"hbm_bytes": int(info.hbm_bytes), "slot_begin": int(info.slot_begin),
                               "slot_count": int(info.slot_count)}
         ok_pc = comm is not None and bool(cfg.get("plants")) and not budget
-        if all_ranks_ok(ok_pc, args.dist_backend) and ok_pc:
+        if args.full and all_ranks_ok(ok_pc, args.dist_backend) and ok_pc:
             wd.phase("the product call (cobs_gpu_sharded_search_batch)", 600)
             out["end_to_end"] = sharded_product_calls(s, comm, cfg, args, world)
     if budget:
@@ -1262,7 +1334,8 @@ def run_bench(args, world, rank, local_rank, wd, emit):
         torch.cuda.empty_cache()
         wd.phase("other forms (--extras)", 1800)
         out["other_forms"] = side_measurements(args, cfg, queries, world, rank, dev, comm)
-    if (world > 1 and not shard_index) or (world == 1 and budget and not shard_index and args.threshold <= 0 and not args.num_results):
+    if args.full and ((world > 1 and not shard_index) or
+                      (world == 1 and budget and not shard_index and args.threshold <= 0 and not args.num_results)):
         # index replicated, one batch per rank (or one GPU streaming a file under a budget: no cpu_baseline leg there):
         # every rank checks a sample of ITS rows against the oracle
         class _Own:
@@ -1272,7 +1345,7 @@ def run_bench(args, world, rank, local_rank, wd, emit):
         own.owned_rows = lambda i: (0, len(queries), batch.counts_tensor())
         own.local_rows = lambda i: batch.counts_tensor()
         out.update(verify_sharded(own, cfg, world, rank, args.dist_backend, exchanged=False))
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not budget and not shard_index:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not budget and not shard_index:
         # the host-buffer calls write their results into this process's memory: the caller sits on the GPU's NUMA node
         # for them (the result array of the default call is 307 MB), and gets all cores back for the CPU baseline
         all_cpus = os.sched_getaffinity(0)
@@ -1284,7 +1357,7 @@ def run_bench(args, world, rank, local_rank, wd, emit):
         os.sched_setaffinity(0, all_cpus)
         out["cpu_baseline"] = cpu_baseline(s, cfg, queries, batch=batch)
         out["bit_exact_vs_oracle"] = out["cpu_baseline"]["bit_exact_vs_gpu"]
-    if (rank == 0 and world == 1 and not budget and not shard_index and args.config == "c3" and args.scale == 1.0
+    if (args.full and rank == 0 and world == 1 and not budget and not shard_index and args.config == "c3" and args.scale == 1.0
             and args.hbm_side_scale > 0 and not args.no_cpu_baseline and not (args.hits_only and args.threshold > 0)
             and not args.num_results):
         # the pin-side view at full occupancy: the same batch against the same geometry at 8x the rows (147 GB resident);

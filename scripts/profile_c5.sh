@@ -8,7 +8,7 @@ REPO=$(pwd)
 OUT=$REPO/gpurun_out/prof_${TAG}_c5
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-python $REPO/bench.py --config c5 --hbm-budget-gb 6 --steps 3 --warmup 1 > "$OUT/bench_c5.json" 2> "$OUT/bench_c5.err"
+python $REPO/bench.py --config c5 --hbm-budget-gb 6 --full --steps 3 --warmup 1 > "$OUT/bench_c5.json" 2> "$OUT/bench_c5.err"
 cd /tmp
 rocprofv3 --kernel-trace --memory-copy-trace --stats --output-format csv -d "$OUT/trace" -o bench -- \
   python $REPO/bench.py --config c5 --hbm-budget-gb 6 --steps 2 --warmup 1 > "$OUT/trace.log" 2>&1

@@ -25,14 +25,14 @@ if not ent or ent.get("kernels_hash") != have:
     sys.exit(1)
 print("traffic stamp matches the kernel source (%s, measured at %s)" % (have, ent.get("git_head")))
 PY
-python bench.py > "$OUT/bench_c3.json" 2> "$OUT/bench_c3.err"
-python bench.py --one-rank-sharded --no-cpu-baseline > "$OUT/bench_c3_one_rank_sharded.json" 2> /dev/null
+python bench.py --full > "$OUT/bench_c3.json" 2> "$OUT/bench_c3.err"
+python bench.py --one-rank-sharded --no-cpu-baseline --full > "$OUT/bench_c3_one_rank_sharded.json" 2> /dev/null
 python scripts/default_call.py 256 > "$OUT/default_call.txt" 2>&1
 python scripts/probes/fresh_buffer_probe.py > "$OUT/fresh_buffer_probe.txt" 2>&1
 python scripts/latency.py > "$OUT/latency.txt" 2>&1
 python scripts/sharded_call.py > "$OUT/sharded_call.txt" 2>&1
 python scripts/probes/default_call_probe.py 16384 > "$OUT/default_call_probe.txt" 2>&1
-(cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o bench -- python "$REPO/bench.py" > "$OUT/bench_c3_profiled.json" 2> "$OUT/trace.err")
+(cd "$TMPDIR" && rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o bench -- python "$REPO/bench.py" --full > "$OUT/bench_c3_profiled.json" 2> "$OUT/trace.err")
 find "$OUT/trace" -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} "$OUT/bench_kernel_stats.csv"
 head -8 "$OUT/bench_kernel_stats.csv" | cut -c1-160
 python - "$OUT/bench_c3.json" <<'PY'

@@ -7,10 +7,10 @@ TAG=${1:-r06}
 OUT=$(pwd)/gpurun_out/stamp_$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-python bench.py --config c5 --no-cpu-baseline --steps 3 --warmup 1 > "$OUT/c5_bench.json" 2> "$OUT/c5_bench.err"
-python bench.py --config c5 --no-cpu-baseline --steps 5 --warmup 2 --queries 256 > "$OUT/c5_q256_bench.json" 2>/dev/null
-COBS_GPU_ROW_RANGES=0 python bench.py --config c5 --no-cpu-baseline --steps 3 --warmup 1 > "$OUT/c5_columns_bench.json" 2>/dev/null
-COBS_GPU_STREAM_PACKED=0 python bench.py --config c5 --no-cpu-baseline --steps 3 --warmup 1 > "$OUT/c5_device_pitch_bench.json" 2>/dev/null
+python bench.py --config c5 --no-cpu-baseline --full --steps 3 --warmup 1 > "$OUT/c5_bench.json" 2> "$OUT/c5_bench.err"
+python bench.py --config c5 --no-cpu-baseline --full --steps 5 --warmup 2 --queries 256 > "$OUT/c5_q256_bench.json" 2>/dev/null
+COBS_GPU_ROW_RANGES=0 python bench.py --config c5 --no-cpu-baseline --full --steps 3 --warmup 1 > "$OUT/c5_columns_bench.json" 2>/dev/null
+COBS_GPU_STREAM_PACKED=0 python bench.py --config c5 --no-cpu-baseline --full --steps 3 --warmup 1 > "$OUT/c5_device_pitch_bench.json" 2>/dev/null
 python scripts/row_fetch_bench.py 1.0 6 > "$OUT/c5_selective.txt" 2>&1
 rm -f /tmp/cobs_c5_1.cobs_compact
 (for m in 2 0; do echo "== streamed shards of the C3 file, 0.75 GB budget each: N mode = 8 $m"; python scripts/shard_times.py 8 $m 10000 0.75; done) > "$OUT/shard_times_streamed.txt" 2>&1
@@ -18,7 +18,7 @@ rm -f /tmp/cobs_c5_1.cobs_compact
 if [ "${2:-}" = "full" ]; then
   # (the box's /tmp is a 79 GB overlay; /dev/shm is tmpfs over its 3 TB of RAM)
   timeout 1500 python bench.py --config c5 --scale 10 --hbm-budget-gb 64 --index-file /dev/shm/cobs_c5_10.cobs_compact \
-      --no-cpu-baseline --steps 2 --warmup 1 > "$OUT/c5_184GB_bench.json" 2> "$OUT/c5_184GB_bench.err"
+      --no-cpu-baseline --full --steps 2 --warmup 1 > "$OUT/c5_184GB_bench.json" 2> "$OUT/c5_184GB_bench.err"
   # the same pass at the CLI's default threshold, hits only: the three streamed sub-indexes are counted in row ranges, the
   # selection runs after each one's last range -- no score rows (round 6; rounds 4-5 wrote 2 GB of them per pass)
   timeout 900 python bench.py --config c5 --scale 10 --hbm-budget-gb 64 --index-file /dev/shm/cobs_c5_10.cobs_compact \

@@ -18,6 +18,11 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def _preload(lib):
+    """the stand-in first, in front of whatever the environment already preloads (which stays)"""
+    return ":".join([lib] + [p for p in os.environ.get("LD_PRELOAD", "").split(":") if p])
+
+
 @pytest.fixture(scope="module")
 def mock_library(gpu_lib):
     r = subprocess.run(["bash", os.path.join(ROOT, "tests", "mock_rccl", "build.sh")], capture_output=True, text=True, timeout=900)
@@ -29,7 +34,7 @@ def mock_library(gpu_lib):
 
 @pytest.mark.parametrize("ranks", [2, 3, 4, 8])
 def test_device_list_handle_over_n_ranks_sharing_the_gpu(mock_library, ranks):
-    env = dict(os.environ, LD_PRELOAD=mock_library)
+    env = dict(os.environ, LD_PRELOAD=_preload(mock_library))
     seed = os.environ.get("COBS_FUZZ_SEED", "0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "mock_rccl", "run_ranks.py"), str(ranks), seed],
                        capture_output=True, text=True, timeout=1500, env=env)
@@ -44,7 +49,7 @@ def test_device_list_handle_with_distinct_device_ordinals(mock_library, ranks):
     thread) -- cobs_gpu_multi_open with devices [0, 1, .., N-1] as on an N-GPU node: the range and duplicate checks,
     one communicator and one index handle per ordinal, every hipSetDevice(ix->device) of the pass / exchange / ranking
     code with an ordinal other than 0.  An ordinal beyond the count is refused before any rank meets another."""
-    env = dict(os.environ, LD_PRELOAD=mock_library, MOCK_RCCL_VIRTUAL_DEVICES=str(ranks))
+    env = dict(os.environ, LD_PRELOAD=_preload(mock_library), MOCK_RCCL_VIRTUAL_DEVICES=str(ranks))
     seed = os.environ.get("COBS_FUZZ_SEED", "0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "mock_rccl", "run_ranks.py"), str(ranks), seed],
                        capture_output=True, text=True, timeout=1500, env=env)
@@ -64,7 +69,7 @@ def test_batch_exchange_entry_points_over_n_ranks(mock_library, ranks):
     _exchange_hits_owned, _exchange_topk -- the calls bench.py's sharded flow and a torch.distributed launcher make,
     one rank per process there -- with N ranks as threads of one process over the stand-in communicator; every rank's
     view afterwards equals the oracle's"""
-    env = dict(os.environ, LD_PRELOAD=mock_library, MOCK_RCCL_TIMEOUT_S="30")
+    env = dict(os.environ, LD_PRELOAD=_preload(mock_library), MOCK_RCCL_TIMEOUT_S="30")
     seed = os.environ.get("COBS_FUZZ_SEED", "0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "mock_rccl", "run_batch_ranks.py"), str(ranks), seed],
                        capture_output=True, text=True, timeout=1500, env=env)
@@ -84,7 +89,7 @@ def test_cli_device_list_over_three_ranks(mock_library, oracle, golden_dir, tmp_
     qf = tmp_path / "q.fa"
     qf.write_text(">first query\n%s\n%s\n\n;second\n%s\n" % (q50[:25], q50[25:], q50[3:40]))
     ixs = [oracle.Index.open(a), oracle.Index.open(b)]
-    env = dict(os.environ, LD_PRELOAD=mock, MOCK_RCCL_TIMEOUT_S="30")     # (the stand-in's marker symbol lets ranks share the device)
+    env = dict(os.environ, LD_PRELOAD=_preload(mock), MOCK_RCCL_TIMEOUT_S="30")     # (the stand-in's marker symbol lets ranks share the device)
     for extra in (["-t", "0.05"], ["-t", "0"], ["-t", "0", "-l", "3"]):
         r = subprocess.run([tool, "-d", "0,0,0", "-i", a, "-i", b, "-f", str(qf)] + extra, capture_output=True, text=True,
                            timeout=300, env=env)
@@ -106,7 +111,7 @@ def test_bench_sharded_flow_over_n_ranks(mock_library, ranks):
     """bench.py's ShardedRun -- the overlapped N > 1 flow the driver's scaling run times: sub-batches, hashing / scan /
     exchange on three streams tied by events, the native all-to-all to query owners -- with N ranks as threads; every
     rank's assembled rows equal the oracle's, for 1, 2 and 3 sub-batches"""
-    env = dict(os.environ, LD_PRELOAD=mock_library, MOCK_RCCL_TIMEOUT_S="30")
+    env = dict(os.environ, LD_PRELOAD=_preload(mock_library), MOCK_RCCL_TIMEOUT_S="30")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "mock_rccl", "run_bench_ranks.py"), str(ranks)],
                        capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0 and r.stdout.strip().startswith("ok "), r.stdout[-3000:] + r.stderr[-8000:]
@@ -115,7 +120,7 @@ def test_bench_sharded_flow_over_n_ranks(mock_library, ranks):
 
 # ---- round 5: faults between the ranks (the one-shot 8-GPU run must not come back empty) ----------
 def _fault(mock_library, case, ranks, timeout_s="8"):
-    env = dict(os.environ, LD_PRELOAD=mock_library, MOCK_RCCL_TIMEOUT_S=timeout_s)
+    env = dict(os.environ, LD_PRELOAD=_preload(mock_library), MOCK_RCCL_TIMEOUT_S=timeout_s)
     return subprocess.run([sys.executable, os.path.join(ROOT, "tests", "mock_rccl", "run_fault_ranks.py"), case, str(ranks)],
                           capture_output=True, text=True, timeout=900, env=env)
 

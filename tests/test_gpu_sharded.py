@@ -72,7 +72,8 @@ def test_bench_sharded_code_path_on_one_rank(gpu_lib):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--one-rank-sharded", "--extras", "--scale", "0.02",
-                        "--queries", "512", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--exchange-chunks", "2"],
+                        "--queries", "512", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--exchange-chunks", "2",
+                        "--full"],
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')][-1]
@@ -116,7 +117,8 @@ def _bench(args, timeout=900, env=None):
     return r, (json.loads(lines[-1]) if lines else None), r.stdout
 
 
-SMALL = ["--scale", "0.02", "--queries", "512", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--exchange-chunks", "2"]
+# (--full: the self-check against the oracle and the product call these tests read are not part of a plain run)
+SMALL = ["--scale", "0.02", "--queries", "512", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--full", "--exchange-chunks", "2"]
 
 
 def test_bench_gpus_1_plain_and_one_rank_sharded(gpu_lib):
