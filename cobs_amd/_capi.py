@@ -60,6 +60,18 @@ class DocEntry(C.Structure):
                 ("term_count", C.c_uint64)]
 
 
+class QuerygenParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("term_size", C.c_uint32), ("num_positive", C.c_uint64),
+                ("num_negative", C.c_uint64), ("size", C.c_uint64), ("seed", C.c_uint64),
+                ("true_negatives", C.c_uint32), ("canonical", C.c_uint32), ("device", C.c_int32),
+                ("text_batch_bytes", C.c_uint32)]
+
+
+class QuerygenStats(C.Structure):
+    _fields_ = [("documents_read", C.c_uint64), ("text_bytes", C.c_uint64), ("terms_probed", C.c_uint64),
+                ("negatives_removed", C.c_uint64), ("kernel_ms", C.c_double)]
+
+
 class Xfer(C.Structure):
     _fields_ = [("peer", C.c_uint64), ("send_offset", C.c_uint64), ("send_bytes", C.c_uint64),
                 ("recv_offset", C.c_uint64), ("recv_bytes", C.c_uint64)]
@@ -126,6 +138,12 @@ SYMBOLS = {
     "cobs_gpu_combine_classic": (_int, [C.POINTER(_cp), _sz, _cp, _u64, _int]),
     "cobs_gpu_combine_compact": (_int, [C.POINTER(_cp), _sz, _cp, _u64]),
     "cobs_gpu_construct_random": (_int, [_cp, _u64, _u64, _u64, _u64, _u64, _int]),
+    "cobs_gpu_generate_queries": (_int, [_vp, C.POINTER(QuerygenParams), C.POINTER(_vp)]),
+    "cobs_gpu_query_set_size": (_sz, [_vp]),
+    "cobs_gpu_query_set_entry": (_int, [_vp, _sz, C.POINTER(C.c_void_p), C.POINTER(_sz), _pu64, _pu64]),
+    "cobs_gpu_query_set_write": (_int, [_vp, _vp, _cp]),
+    "cobs_gpu_query_set_stats": (_int, [_vp, C.POINTER(QuerygenStats)]),
+    "cobs_gpu_query_set_free": (None, [_vp]),
     "cobs_gpu_search": (_int, [_vp, _cp, _sz, _dbl, _sz, C.POINTER(Hit), _sz, C.POINTER(_sz)]),
     "cobs_gpu_search_batch": (_int, [_vp, C.POINTER(_cp), C.POINTER(_sz), _sz, _dbl, _sz,
                                      C.POINTER(Hit), _sz, C.POINTER(_sz), C.POINTER(_sz)]),

@@ -26,23 +26,11 @@
 
 #include "documents.hpp"
 #include "engine.hpp"
+#include "staging.hpp"
 
 using namespace cobs_amd;
 
-__attribute__((visibility("hidden"))) cobs_gpu_status cobs_gpu_set_error(cobs_gpu_status st, const char* msg);   // engine.cpp
-
 namespace {
-
-#define BUILD_TRY(expr)                                                             \
-    do {                                                                            \
-        hipError_t _e = (expr);                                                     \
-        if (_e != hipSuccess) {                                                     \
-            const bool nodev = _e == hipErrorNoDevice || _e == hipErrorInvalidDevice; \
-            std::string m = std::string(#expr) + ": " + hipGetErrorString(_e);      \
-            (void)hipGetLastError();                                                \
-            return cobs_gpu_set_error(nodev ? COBS_GPU_ERR_NO_DEVICE : COBS_GPU_ERR_HIP, m.c_str()); \
-        }                                                                           \
-    } while (0)
 
 struct DevMem {
     void* p = nullptr;
@@ -102,33 +90,8 @@ cobs_gpu_status read_params(const cobs_gpu_build_params* p, Params& out) {
     return COBS_GPU_OK;
 }
 
-cobs_gpu_status pick_device(int device) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
-        (void)hipGetLastError();
-        return cobs_gpu_set_error(COBS_GPU_ERR_NO_DEVICE, "no HIP device visible; libcobs_gpu has no CPU fallback");
-    }
-    if (device >= 0) {
-        if (device >= n) return cobs_gpu_set_error(COBS_GPU_ERR_ARG, "device ordinal out of range");
-        BUILD_TRY(hipSetDevice(device));
-    }
-    return COBS_GPU_OK;
-}
-
-// ---- where the documents come from ---------------------------------------------------------------
-struct DocSource {
-    virtual ~DocSource() = default;
-    virtual size_t size() const = 0;
-    virtual const char* name(size_t d) const = 0;
-    virtual uint64_t terms(size_t d, uint32_t k) const = 0;          // what sizes a signature
-    virtual uint64_t text_bound(size_t d, uint32_t k) const = 0;     // upper bound of the document's term text
-    virtual bool parses() const = 0;                                 // loading reads and parses files
-    // the document's term text into `out` (a span of the staging buffer), its stretches into `segs`
-    virtual cobs_gpu_status load(size_t d, uint32_t k, TermSink& out, std::vector<TermSeg>& segs,
-                                 std::string& scratch) const = 0;
-};
-
-// documents handed over as texts (cobs_gpu_build_classic / _compact / _index)
+// ArraySource: documents handed over as texts (cobs_gpu_build_classic / _compact / _index); the
+// document list's ListSource and the batch producer are in staging.hpp
 struct ArraySource final : DocSource {
     const char* const* names;
     const char* const* texts;
@@ -150,221 +113,32 @@ struct ArraySource final : DocSource {
     }
 };
 
-// a document list (cobs_gpu_build_*_list)
-struct ListSource final : DocSource {
-    const std::vector<DocEntry>& list;
-    explicit ListSource(const std::vector<DocEntry>& l) : list(l) {}
-    size_t size() const override { return list.size(); }
-    const char* name(size_t d) const override { return list[d].name.c_str(); }
-    uint64_t terms(size_t d, uint32_t k) const override { return num_terms(list[d], k); }
-    uint64_t text_bound(size_t d, uint32_t k) const override { return term_text_bound(list[d], k); }
-    bool parses() const override { return true; }
-    cobs_gpu_status load(size_t d, uint32_t k, TermSink& out, std::vector<TermSeg>& segs, std::string& scratch) const override {
-        return load_terms(list[d], k, out, segs, scratch);
-    }
-};
-
-// Documents reach the device in batches of at most this many bytes of term text (the reference
-// batches documents by a memory budget too: classic_index.cpp:565-659 builds one small index per
-// batch and interleaves them afterwards; here every batch sets its bits straight at the documents'
-// final columns of the one matrix in HBM, so there is nothing to combine).
-constexpr uint64_t kTextBatchBytes = 256ull << 20;
-constexpr size_t kTextPad = 64;                 // readable bytes behind the text (build_kernel loads dwords)
-// staging sets of a build: one being parsed into, one on its way over PCIe, one being hashed (with two,
-// parsing waits for the kernel of the batch before last: 8.2 ms per 256 MiB batch instead of 6)
-constexpr int kStages = 3;
-
-// One of the staging sets of a build: pinned term text + stretch tables, their device copies,
-// the event that tells when the GPU is done with them.  Host threads parse documents straight into
-// `text` (every document of a batch owns a span sized by its text bound; what it leaves unused is
-// a gap stretch the kernel skips), so a character is written once between the file and the H2D copy.
-struct Stage {
-    PinnedBuf<uint8_t> text;
-    PinnedBuf<uint64_t> seg_off;
-    PinnedBuf<uint32_t> seg_col;
-    DevBuf<uint8_t> d_text;
-    DevBuf<uint64_t> d_off;
-    DevBuf<uint32_t> d_col;
-    hipEvent_t done = nullptr, copied = nullptr;
-    bool busy = false;
-    ~Stage() {
-        if (done) (void)hipEventDestroy(done);
-        if (copied) (void)hipEventDestroy(copied);
-    }
-};
-
-// Staging memory outlives a build: pinning 2 x 256 MiB costs more than hashing them.  The sets are
-// checked out per build and handed back; never freed (a static destructor would run after the HIP
-// runtime's own).
-struct StagePool {
-    std::mutex mu;
-    std::vector<Stage*> idle;
-    std::vector<DevBuf<uint8_t>*> idle_planes;     // byte-map planes (one buffer per build in flight)
-    int device = -1;
-    DevBuf<uint8_t>* take_planes(int dev) {
-        std::lock_guard<std::mutex> g(mu);
-        if (device != dev) {
-            for (Stage* s : idle) delete s;
-            idle.clear();
-            for (auto* b : idle_planes) delete b;
-            idle_planes.clear();
-            device = dev;
-        }
-        if (idle_planes.empty()) return new DevBuf<uint8_t>;
-        DevBuf<uint8_t>* b = idle_planes.back();
-        idle_planes.pop_back();
-        return b;
-    }
-    void give_planes(DevBuf<uint8_t>* b) {
-        std::lock_guard<std::mutex> g(mu);
-        idle_planes.push_back(b);
-    }
-    void release_idle() {
-        std::lock_guard<std::mutex> g(mu);
-        for (Stage* s : idle) delete s;
-        idle.clear();
-        for (auto* b : idle_planes) delete b;
-        idle_planes.clear();
-    }
-    Stage* take(int dev) {
-        std::lock_guard<std::mutex> g(mu);
-        if (device != dev) {                    // buffers belong to the device they were made on
-            for (Stage* s : idle) delete s;
-            idle.clear();
-            for (auto* b : idle_planes) delete b;
-            idle_planes.clear();
-            device = dev;
-        }
-        if (idle.empty()) return new Stage;
-        Stage* s = idle.back();
-        idle.pop_back();
-        return s;
-    }
-    void give(Stage* s) {
-        std::lock_guard<std::mutex> g(mu);
-        idle.push_back(s);
-    }
-};
-StagePool& stage_pool() {
-    static StagePool* pool = new StagePool;
-    return *pool;
-}
-
-// Host threads that stay up for a whole build: a batch hands them one job (parse the documents of
-// the batch), run() returns when every worker has finished it.  Spawning 64-128 threads per batch
-// cost 1-2 ms of the ~6 ms a batch has.
-class WorkerPool {
-public:
-    explicit WorkerPool(size_t n) {
-        for (size_t t = 0; t < n; ++t) threads_.emplace_back([this, t]() { loop(t); });
-    }
-    ~WorkerPool() {
-        {
-            std::lock_guard<std::mutex> g(mu_);
-            quit_ = true;
-            ++gen_;
-        }
-        cv_.notify_all();
-        for (auto& t : threads_) t.join();
-    }
-    size_t size() const { return threads_.size(); }
-    void run(const std::function<void(size_t)>& fn) {
-        {
-            std::lock_guard<std::mutex> g(mu_);
-            job_ = &fn;
-            done_ = 0;
-            ++gen_;
-        }
-        cv_.notify_all();
-        std::unique_lock<std::mutex> lk(mu_);
-        cv_done_.wait(lk, [&] { return done_ == threads_.size(); });
-        job_ = nullptr;
-    }
-
-private:
-    void loop(size_t tid) {
-        uint64_t seen = 0;
-        for (;;) {
-            const std::function<void(size_t)>* job;
-            {
-                std::unique_lock<std::mutex> lk(mu_);
-                cv_.wait(lk, [&] { return gen_ != seen; });
-                seen = gen_;
-                if (quit_) return;
-                job = job_;
-            }
-            (*job)(tid);
-            {
-                std::lock_guard<std::mutex> g(mu_);
-                ++done_;
-            }
-            cv_done_.notify_one();
-        }
-    }
-    std::vector<std::thread> threads_;
-    std::mutex mu_;
-    std::condition_variable cv_, cv_done_;
-    const std::function<void(size_t)>* job_ = nullptr;
-    uint64_t gen_ = 0;
-    size_t done_ = 0;
-    bool quit_ = false;
-};
-
-struct Slot {                                   // one document of a batch
-    size_t doc_col;                             // its column
-    size_t src;                                 // its index in the source
-    uint64_t begin, cap;                        // its span of the staging text
-    uint64_t used = 0;
-    std::vector<TermSeg> segs;
-    cobs_gpu_status status = COBS_GPU_OK;
-    std::string error;
-};
-
 // What one build call keeps across its matrices (a compact index is one build_into per
-// sub-index): the two streams, the staging sets and byte planes checked out of the pool, the
-// parser threads and their scratch buffers.
+// sub-index): the staging context (streams, staging sets, parser threads) and the byte planes
+// checked out of the pool.
 struct BuildContext {
-    hipStream_t stream = nullptr, copy_stream = nullptr;   // kernels | uploads (batch i + 1 beside the kernel of batch i)
-    Stage* st[kStages] = {};
+    StagingContext sc;
     DevBuf<uint8_t>* planes = nullptr;
-    std::unique_ptr<WorkerPool> workers;                   // created by the first batch with more than one document
-    std::vector<std::string> scratch;                      // the file being parsed, one per worker, reused
-    size_t max_threads = 1;
-    bool ready = false;
     // writing an index file: the matrix of the current (sub-)index and the two pinned buffers its
     // rows leave through -- allocated once per build, not once per sub-index
     DevBuf<uint8_t> matrix;
     PinnedBuf<uint8_t> out_host[2];
 
     cobs_gpu_status init(bool parses) {
-        if (ready) return COBS_GPU_OK;
+        if (sc.ready) return COBS_GPU_OK;
+        cobs_gpu_status st = sc.init(parses);
+        if (st != COBS_GPU_OK) return st;
         int dev = 0;
         BUILD_TRY(hipGetDevice(&dev));
-        BUILD_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-        BUILD_TRY(hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking));
-        for (Stage*& s : st) {
-            s = stage_pool().take(dev);
-            if (!s->done) BUILD_TRY(hipEventCreateWithFlags(&s->done, hipEventDisableTiming));
-            if (!s->copied) BUILD_TRY(hipEventCreateWithFlags(&s->copied, hipEventDisableTiming));
-        }
         planes = stage_pool().take_planes(dev);
-        const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-        max_threads = parses ? std::min<size_t>(hw, 128) : std::min<size_t>(hw, 8);
-        scratch.resize(max_threads);
-        ready = true;
         return COBS_GPU_OK;
     }
     BuildContext() = default;
     BuildContext(const BuildContext&) = delete;
     BuildContext& operator=(const BuildContext&) = delete;
     ~BuildContext() {
-        workers.reset();
-        if (copy_stream) { (void)hipStreamSynchronize(copy_stream); (void)hipStreamDestroy(copy_stream); }
-        if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
-        // handed back last-to-first: the next build takes the set that was used first (and has its
-        // buffers) as its first set again
-        for (int i = kStages - 1; i >= 0; --i)
-            if (st[i]) { st[i]->busy = false; stage_pool().give(st[i]); }
+        if (sc.copy_stream) (void)hipStreamSynchronize(sc.copy_stream);
+        if (sc.stream) (void)hipStreamSynchronize(sc.stream);
         if (planes) stage_pool().give_planes(planes);
     }
 };
@@ -378,111 +152,27 @@ cobs_gpu_status build_into(BuildContext& ctx, uint32_t* d_matrix, uint64_t sig, 
     if (n >= (kBuildRawStretch - 1)) return cobs_gpu_set_error(COBS_GPU_ERR_UNSUPPORTED, "too many documents in one matrix");
     cobs_gpu_status ist = ctx.init(src.parses());
     if (ist != COBS_GPU_OK) return ist;
-    hipStream_t stream = ctx.stream, copy_stream = ctx.copy_stream;
+    hipStream_t stream = ctx.sc.stream;
     struct { DevBuf<uint8_t>* planes; } guard{ctx.planes};
-    Stage* const* stage = ctx.st;
     // byte-map planes of a batch: one byte per (document of the batch, signature row)
     const uint64_t bm_stride = (sig + 255) / 256 * 256;
     constexpr uint64_t kPlaneBudget = 3ull << 30;
 
     // COBS_GPU_BUILD_TRACE=1: where the host side of a build spends its time (stderr, one line per build)
     static const bool trace = std::getenv("COBS_GPU_BUILD_TRACE") != nullptr;
-    double t_wait = 0, t_parse = 0, t_table = 0, t_issue = 0;
+    StageTimes tm;
+    double t_issue = 0;
     auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const size_t max_threads = ctx.max_threads;
-    std::vector<Slot> slots;
-    std::vector<std::string>& scratch = ctx.scratch;
-    std::unique_ptr<WorkerPool>& workers = ctx.workers;
+    StagedBatch batch;
     int cur = 0;
     for (size_t b0 = 0; b0 < n;) {
-        // documents [b0, b1): as many as fit the batch by their text bounds (at least one)
-        slots.clear();
-        uint64_t total = 0;
-        size_t b1 = b0;
-        while (b1 < n) {
-            const uint64_t bound = src.text_bound(docs[b1], pr.term_size);
-            if (b1 > b0 && total + bound > text_batch) break;
-            Slot sl;
-            sl.doc_col = b1;
-            sl.src = docs[b1];
-            sl.begin = total;
-            sl.cap = bound;
-            slots.push_back(std::move(sl));
-            total += bound;
-            ++b1;
-        }
-        Stage& s = *stage[cur];
-        double t0 = now();
-        if (s.busy) { BUILD_TRY(hipEventSynchronize(s.done)); s.busy = false; }
-        BUILD_TRY(s.text.reserve((size_t)std::max<uint64_t>(total, text_batch) + kTextPad));
-        t_wait += now() - t0;
-        t0 = now();
-        // parse: every worker takes the next document and writes its term text into its span
-        std::atomic<size_t> next{0};
-        auto work = [&](size_t tid) {
-            for (size_t i; (i = next.fetch_add(1)) < slots.size();) {
-                Slot& sl = slots[i];
-                TermSink sink;
-                sink.data = reinterpret_cast<char*>(s.text.p) + sl.begin;
-                sink.cap = (size_t)sl.cap;
-                sl.status = src.load(sl.src, pr.term_size, sink, sl.segs, scratch[tid]);
-                if (sl.status == COBS_GPU_OK && sink.overflow) {
-                    sl.status = COBS_GPU_ERR_FORMAT;
-                    sl.error = "a document outgrew the size its list entry recorded";
-                } else if (sl.status != COBS_GPU_OK) {
-                    sl.error = cobs_gpu_last_error();
-                }
-                sl.used = sink.size;
-            }
-        };
-        if (max_threads <= 1 || slots.size() <= 1) {
-            work(0);
-        } else {
-            // as many workers as the largest batch so far has documents (a compact build may start
-            // with a small sub-index and go on to large ones)
-            const size_t want = std::min(max_threads, std::max<size_t>(slots.size(), 8));
-            if (!workers || workers->size() < want) workers.reset(new WorkerPool(want));
-            workers->run(work);
-        }
-        t_parse += now() - t0;
-        t0 = now();
-        // the stretch table: a document's stretches, the rest of its span as a gap
-        size_t nsegs = 0;
-        for (const Slot& sl : slots) {
-            if (sl.status != COBS_GPU_OK) return cobs_gpu_set_error(sl.status, sl.error.c_str());
-            nsegs += 2 * sl.segs.size() + 2;
-        }
-        BUILD_TRY(s.seg_off.reserve(nsegs + 1));
-        BUILD_TRY(s.seg_col.reserve(nsegs + 1));
-        size_t ns = 0;
-        auto add = [&](uint64_t off, uint32_t col) {
-            if (ns && s.seg_off.p[ns - 1] == off) { s.seg_col.p[ns - 1] = col; return; }   // the previous one was empty
-            s.seg_off.p[ns] = off;
-            s.seg_col.p[ns] = col;
-            ++ns;
-        };
-        for (const Slot& sl : slots) {
-            uint64_t at = sl.begin;                         // everything before `at` is described
-            for (const TermSeg& g : sl.segs) {
-                if (g.len == 0) continue;
-                if (sl.begin + g.begin > at) add(at, kBuildGapStretch);
-                add(sl.begin + g.begin, (uint32_t)sl.doc_col | (g.raw ? kBuildRawStretch : 0u));
-                at = sl.begin + g.begin + g.len;
-            }
-            if (at < sl.begin + sl.cap) add(at, kBuildGapStretch);
-        }
-        s.seg_off.p[ns] = total;
-        t_table += now() - t0;
-        t0 = now();
+        cobs_gpu_status bst = stage_batch(ctx.sc, cur, src, docs, b0, n, pr.term_size, text_batch, batch, tm);
+        if (bst != COBS_GPU_OK) return bst;
+        const size_t b1 = batch.b1, ns = batch.nsegs;
+        const uint64_t total = batch.total;
+        Stage& s = *batch.stage;
+        const double t0 = now();
         if (ns && total) {
-            BUILD_TRY(s.d_text.reserve(s.text.cap));
-            BUILD_TRY(s.d_off.reserve(s.seg_off.cap));
-            BUILD_TRY(s.d_col.reserve(s.seg_col.cap));
-            BUILD_TRY(hipMemcpyAsync(s.d_text.p, s.text.p, (size_t)total, hipMemcpyHostToDevice, copy_stream));
-            BUILD_TRY(hipMemcpyAsync(s.d_off.p, s.seg_off.p, (ns + 1) * 8, hipMemcpyHostToDevice, copy_stream));
-            BUILD_TRY(hipMemcpyAsync(s.d_col.p, s.seg_col.p, ns * 4, hipMemcpyHostToDevice, copy_stream));
-            BUILD_TRY(hipEventRecord(s.copied, copy_stream));
-            BUILD_TRY(hipStreamWaitEvent(stream, s.copied, 0));
             BuildArgs a;
             a.text = s.d_text.p;
             a.seg_off = s.d_off.p;
@@ -525,8 +215,7 @@ cobs_gpu_status build_into(BuildContext& ctx, uint32_t* d_matrix, uint64_t sig, 
                 pk.ndocs = (uint32_t)(b1 - b0);
                 BUILD_TRY(launch_pack_bytemap(pk, stream));
             }
-            BUILD_TRY(hipEventRecord(s.done, stream));
-            s.busy = true;
+            if ((bst = finish_batch(ctx.sc, batch)) != COBS_GPU_OK) return bst;
         }
         t_issue += now() - t0;
         cur = (cur + 1) % kStages;                          // the next set is parsed into while this one is uploaded and hashed
@@ -536,7 +225,7 @@ cobs_gpu_status build_into(BuildContext& ctx, uint32_t* d_matrix, uint64_t sig, 
     BUILD_TRY(hipStreamSynchronize(stream));
     if (trace)
         std::fprintf(stderr, "[cobs_gpu build] %zu documents: wait for a staging set %.3f s, parse %.3f s, stretch table %.3f s, "
-                             "issue %.3f s, drain %.3f s\n", n, t_wait, t_parse, t_table, t_issue, now() - t0);
+                             "issue %.3f s, drain %.3f s\n", n, tm.wait, tm.parse, tm.table, tm.upload + t_issue, now() - t0);
     return COBS_GPU_OK;
 }
 
@@ -818,6 +507,169 @@ cobs_gpu_status build_from_list(bool compact, const cobs_gpu_doclist* dl, const 
 }
 
 }  // namespace
+
+// ---- the batch producer (staging.hpp) -------------------------------------------------------------
+namespace cobs_amd {
+
+cobs_gpu_status pick_device(int device) {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
+        (void)hipGetLastError();
+        return cobs_gpu_set_error(COBS_GPU_ERR_NO_DEVICE, "no HIP device visible; libcobs_gpu has no CPU fallback");
+    }
+    if (device >= 0) {
+        if (device >= n) return cobs_gpu_set_error(COBS_GPU_ERR_ARG, "device ordinal out of range");
+        BUILD_TRY(hipSetDevice(device));
+    }
+    return COBS_GPU_OK;
+}
+
+StagePool& stage_pool() {
+    static StagePool* pool = new StagePool;
+    return *pool;
+}
+
+cobs_gpu_status StagingContext::init(bool parses) {
+    if (ready) return COBS_GPU_OK;
+    int dev = 0;
+    BUILD_TRY(hipGetDevice(&dev));
+    BUILD_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    BUILD_TRY(hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking));
+    for (Stage*& s : st) {
+        s = stage_pool().take(dev);
+        if (!s->done) BUILD_TRY(hipEventCreateWithFlags(&s->done, hipEventDisableTiming));
+        if (!s->copied) BUILD_TRY(hipEventCreateWithFlags(&s->copied, hipEventDisableTiming));
+    }
+    const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
+    max_threads = parses ? std::min<size_t>(hw, 128) : std::min<size_t>(hw, 8);
+    scratch.resize(max_threads);
+    ready = true;
+    return COBS_GPU_OK;
+}
+
+StagingContext::~StagingContext() {
+    workers.reset();
+    if (copy_stream) { (void)hipStreamSynchronize(copy_stream); (void)hipStreamDestroy(copy_stream); }
+    if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
+    // handed back last-to-first: the next build takes the set that was used first (and has its
+    // buffers) as its first set again
+    for (int i = kStages - 1; i >= 0; --i)
+        if (st[i]) { st[i]->busy = false; stage_pool().give(st[i]); }
+}
+
+cobs_gpu_status stage_batch(StagingContext& ctx, int cur, const DocSource& src, const size_t* docs, size_t b0, size_t n,
+                            uint32_t term_size, uint64_t text_batch, StagedBatch& out, StageTimes& tm) {
+    auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    const size_t max_threads = ctx.max_threads;
+    std::vector<Slot>& slots = out.slots;
+    std::vector<std::string>& scratch = ctx.scratch;
+    std::unique_ptr<WorkerPool>& workers = ctx.workers;
+    // documents [b0, b1): as many as fit the batch by their text bounds (at least one)
+    slots.clear();
+    uint64_t total = 0;
+    size_t b1 = b0;
+    while (b1 < n) {
+        const uint64_t bound = src.text_bound(docs[b1], term_size);
+        if (b1 > b0 && total + bound > text_batch) break;
+        Slot sl;
+        sl.doc_col = b1;
+        sl.src = docs[b1];
+        sl.begin = total;
+        sl.cap = bound;
+        slots.push_back(std::move(sl));
+        total += bound;
+        ++b1;
+    }
+    Stage& s = *ctx.st[cur];
+    out.stage = &s;
+    out.b0 = b0;
+    out.b1 = b1;
+    out.total = total;
+    out.nsegs = 0;
+    double t0 = now();
+    if (s.busy) { BUILD_TRY(hipEventSynchronize(s.done)); s.busy = false; }
+    BUILD_TRY(s.text.reserve((size_t)std::max<uint64_t>(total, text_batch) + kTextPad));
+    tm.wait += now() - t0;
+    t0 = now();
+    // parse: every worker takes the next document and writes its term text into its span
+    std::atomic<size_t> next{0};
+    auto work = [&](size_t tid) {
+        for (size_t i; (i = next.fetch_add(1)) < slots.size();) {
+            Slot& sl = slots[i];
+            TermSink sink;
+            sink.data = reinterpret_cast<char*>(s.text.p) + sl.begin;
+            sink.cap = (size_t)sl.cap;
+            sl.status = src.load(sl.src, term_size, sink, sl.segs, scratch[tid]);
+            if (sl.status == COBS_GPU_OK && sink.overflow) {
+                sl.status = COBS_GPU_ERR_FORMAT;
+                sl.error = "a document outgrew the size its list entry recorded";
+            } else if (sl.status != COBS_GPU_OK) {
+                sl.error = cobs_gpu_last_error();
+            }
+            sl.used = sink.size;
+        }
+    };
+    if (max_threads <= 1 || slots.size() <= 1) {
+        work(0);
+    } else {
+        // as many workers as the largest batch so far has documents (a compact build may start
+        // with a small sub-index and go on to large ones)
+        const size_t want = std::min(max_threads, std::max<size_t>(slots.size(), 8));
+        if (!workers || workers->size() < want) workers.reset(new WorkerPool(want));
+        workers->run(work);
+    }
+    tm.parse += now() - t0;
+    t0 = now();
+    // the stretch table: a document's stretches, the rest of its span as a gap
+    size_t nsegs = 0;
+    for (const Slot& sl : slots) {
+        if (sl.status != COBS_GPU_OK) return cobs_gpu_set_error(sl.status, sl.error.c_str());
+        nsegs += 2 * sl.segs.size() + 2;
+    }
+    BUILD_TRY(s.seg_off.reserve(nsegs + 1));
+    BUILD_TRY(s.seg_col.reserve(nsegs + 1));
+    size_t ns = 0;
+    auto add = [&](uint64_t off, uint32_t col) {
+        if (ns && s.seg_off.p[ns - 1] == off) { s.seg_col.p[ns - 1] = col; return; }   // the previous one was empty
+        s.seg_off.p[ns] = off;
+        s.seg_col.p[ns] = col;
+        ++ns;
+    };
+    for (const Slot& sl : slots) {
+        uint64_t at = sl.begin;                         // everything before `at` is described
+        for (const TermSeg& g : sl.segs) {
+            if (g.len == 0) continue;
+            if (sl.begin + g.begin > at) add(at, kBuildGapStretch);
+            add(sl.begin + g.begin, (uint32_t)sl.doc_col | (g.raw ? kBuildRawStretch : 0u));
+            at = sl.begin + g.begin + g.len;
+        }
+        if (at < sl.begin + sl.cap) add(at, kBuildGapStretch);
+    }
+    s.seg_off.p[ns] = total;
+    out.nsegs = ns;
+    tm.table += now() - t0;
+    t0 = now();
+    if (ns && total) {
+        BUILD_TRY(s.d_text.reserve(s.text.cap));
+        BUILD_TRY(s.d_off.reserve(s.seg_off.cap));
+        BUILD_TRY(s.d_col.reserve(s.seg_col.cap));
+        BUILD_TRY(hipMemcpyAsync(s.d_text.p, s.text.p, (size_t)total, hipMemcpyHostToDevice, ctx.copy_stream));
+        BUILD_TRY(hipMemcpyAsync(s.d_off.p, s.seg_off.p, (ns + 1) * 8, hipMemcpyHostToDevice, ctx.copy_stream));
+        BUILD_TRY(hipMemcpyAsync(s.d_col.p, s.seg_col.p, ns * 4, hipMemcpyHostToDevice, ctx.copy_stream));
+        BUILD_TRY(hipEventRecord(s.copied, ctx.copy_stream));
+        BUILD_TRY(hipStreamWaitEvent(ctx.stream, s.copied, 0));
+    }
+    tm.upload += now() - t0;
+    return COBS_GPU_OK;
+}
+
+cobs_gpu_status finish_batch(StagingContext& ctx, StagedBatch& b) {
+    BUILD_TRY(hipEventRecord(b.stage->done, ctx.stream));
+    b.stage->busy = true;
+    return COBS_GPU_OK;
+}
+
+}  // namespace cobs_amd
 
 extern "C" {
 

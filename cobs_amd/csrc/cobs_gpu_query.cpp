@@ -35,6 +35,8 @@ static void usage() {
                  "        always lives in HBM, or is streamed through it under --hbm-budget)\n"
                  "       cobs_gpu_query classic-construct | compact-construct | classic-combine | compact-construct-combine ...\n"
                  "        (the construction sub-tools of `cobs`, same arguments; see cobs_gpu_tools.cpp)\n"
+                 "       cobs_gpu_query generate-queries PATH [-k K] [-p N] [-n N] [-N] [-s SIZE] [-S SEED] [-o OUT]\n"
+                 "                      [--file-type T] [--canonical] [-d DEVICE]   (`cobs generate-queries`, same flags)\n"
                  "       cobs_gpu_query --benchmark -i INDEX [-k KMERS] [-q QUERIES] [-w WARMUP] [--seed S] [--dist]\n"
                  "       cobs_gpu_query benchmark-fpr INDEX [-k KMERS] [-q QUERIES] [-w WARMUP] [-d|--dist] [--seed S] [--device N[,M..]]\n"
                  "        (`cobs benchmark-fpr`, same flags: -d / --dist adds the distribution of all scores,\n"

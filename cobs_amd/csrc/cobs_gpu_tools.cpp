@@ -7,6 +7,8 @@
 //   cobs_gpu_query compact-construct INPUT OUT.cobs_compact [flags] [-p PAGE]     (:294-380)
 //   cobs_gpu_query classic-combine IN_DIR OUT.cobs_classic                        (:1044-1060)
 //   cobs_gpu_query compact-construct-combine IN_DIR OUT.cobs_compact [-p PAGE]   (:383-408)
+//   cobs_gpu_query generate-queries PATH [-k K] [-p N] [-n N] [-N] [-s SIZE] [-S SEED] [-o OUT]
+//                  [--file-type T] [--canonical] [-d DEVICE]                        (:734-959)
 //
 // Flags of the two constructors: --file-type, -h/--num-hashes, -f/--false-positive-rate,
 // -k/--term-size, --no-canonicalize, -C/--clobber, --continue; -m/--memory, -T/--threads,
@@ -19,6 +21,7 @@
 #include <cstring>
 #include <filesystem>
 #include <iostream>
+#include <random>
 #include <string>
 #include <vector>
 
@@ -275,6 +278,62 @@ int print_kmers(int argc, char** argv) {
 
 }  // namespace
 
+// `cobs generate-queries PATH [flags]` (reference src/cobs.cpp:734-959): the query file on stdout (or
+// -o), the reference's LOG lines on stderr.  -T/--threads is accepted and ignored; --canonical
+// (no reference counterpart) compares canonical k-mers for -N; -d/--device selects the GPU.
+int generate_queries_tool(int argc, char** argv) {
+    std::vector<std::string> positional;
+    std::string file_type = "any", out_file;
+    cobs_gpu_querygen_params p{};
+    p.struct_size = sizeof p;
+    p.term_size = 31;
+    p.device = -1;
+    bool have_seed = false;
+    for (int i = 0; i < argc; ++i) {
+        const std::string a = argv[i];
+        auto need = [&]() -> const char* {
+            if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", a.c_str()); std::exit(1); }
+            return argv[++i];
+        };
+        if (a == "--file-type") file_type = need();
+        else if (a == "-k" || a == "--term-size") p.term_size = (uint32_t)std::strtoul(need(), nullptr, 10);
+        else if (a == "-p" || a == "--positive") p.num_positive = std::strtoull(need(), nullptr, 10);
+        else if (a == "-n" || a == "--negative") p.num_negative = std::strtoull(need(), nullptr, 10);
+        else if (a == "-N" || a == "--true-negative") p.true_negatives = 1;
+        else if (a == "-s" || a == "--size") p.size = std::strtoull(need(), nullptr, 10);
+        else if (a == "-S" || a == "--seed") { p.seed = std::strtoull(need(), nullptr, 10); have_seed = true; }
+        else if (a == "-o" || a == "--out-file") out_file = need();
+        else if (a == "-T" || a == "--threads") (void)need();
+        else if (a == "--canonical") p.canonical = 1;
+        else if (a == "-d" || a == "--device") p.device = std::atoi(need());
+        else if (!a.empty() && a[0] == '-' && a.size() > 1) { std::fprintf(stderr, "unknown flag %s\n", a.c_str()); return 1; }
+        else positional.push_back(a);
+    }
+    if (positional.size() != 1) {
+        std::fprintf(stderr, "usage: cobs_gpu_query generate-queries PATH [-k K] [-p N] [-n N] [-N] [-s SIZE] [-S SEED] "
+                             "[-o OUT] [--file-type T] [--canonical] [-d DEVICE]\n");
+        return 1;
+    }
+    if (!have_seed) {
+        p.seed = ((uint64_t)std::random_device{}() << 32) | std::random_device{}();
+        std::cerr << "seed: " << p.seed << '\n';
+    }
+    try {
+        const cobs_gpu::DocumentList filelist(positional[0], cobs_gpu::StringToFileType(file_type));
+        uint64_t total_terms = 0;
+        for (size_t d = 0; d < filelist.size(); ++d) total_terms += filelist[d].num_terms(p.term_size);
+        std::cerr << "Given " << filelist.size() << " documents containing " << total_terms << " " << p.term_size
+                  << "-gram terms" << '\n';
+        const cobs_gpu::QuerySet set(filelist, p);
+        if (p.true_negatives) std::cerr << "removed " << set.stats().negatives_removed << " false negatives" << '\n';
+        set.write(out_file);
+    } catch (const cobs_gpu::Error& e) {
+        std::fprintf(stderr, "EXCEPTION: %s\n", e.what());
+        return 1;
+    }
+    return 0;
+}
+
 // -> -1 if argv[1] is not one of the sub-tools, else the exit code
 static int tools(int argc, char** argv);
 
@@ -292,6 +351,7 @@ static int tools(int argc, char** argv) {
     if (argc < 2) return -1;
     const std::string tool = argv[1];
     if (tool == "doc-list") return doc_tool(argc - 2, argv + 2, false);
+    if (tool == "generate-queries") return generate_queries_tool(argc - 2, argv + 2);
     if (tool == "doc-dump") return doc_tool(argc - 2, argv + 2, true);
     if (tool == "print-parameters") return print_parameters(argc - 2, argv + 2);
     if (tool == "print-kmers") return print_kmers(argc - 2, argv + 2);

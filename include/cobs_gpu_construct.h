@@ -150,6 +150,53 @@ cobs_gpu_status cobs_gpu_combine_compact(const char* const* in_paths, size_t n, 
 cobs_gpu_status cobs_gpu_construct_random(const char* out_path, uint64_t signature_size, uint64_t num_documents,
                                           uint64_t document_size, uint64_t num_hashes, uint64_t seed, int device);
 
+
+/* ---- generate-queries (reference src/cobs.cpp:734-959) ------------------------------------------
+ * Labelled query sets from a document list: positives are random terms of the documents (their
+ * document and term index recorded), negatives random ACGT sequences; with true_negatives every
+ * document term is looked up on the GPU and a negative holding one of them is dropped.  The random
+ * stream is this library's own: draw i of seed S is splitmix64's finaliser of S + (i + 1) * 0x9E3779B97F4A7C15
+ * (positive indices, then the negative candidates' bases, then the padding, then the shuffle); the
+ * same seed gives the same set on any device and at any text batch size. */
+typedef struct cobs_gpu_querygen_params {
+    uint32_t struct_size;        /* sizeof(cobs_gpu_querygen_params) */
+    uint32_t term_size;          /* -k, default 31 */
+    uint64_t num_positive;       /* -p */
+    uint64_t num_negative;       /* -n */
+    uint64_t size;               /* -s: query length (below term_size means term_size) */
+    uint64_t seed;               /* -S */
+    uint32_t true_negatives;     /* -N: drop negatives that share a term with a document */
+    uint32_t canonical;          /* compare canonical k-mers instead of raw ones (no reference counterpart) */
+    int32_t device;              /* -1 = current */
+    uint32_t text_batch_bytes;   /* documents are scanned in batches of at most this much text (0 = 256 MiB) */
+} cobs_gpu_querygen_params;
+
+typedef struct cobs_gpu_query_set cobs_gpu_query_set;
+typedef struct cobs_gpu_querygen_stats {
+    uint64_t documents_read;     /* documents parsed and scanned (without -N only those holding positives) */
+    uint64_t text_bytes;         /* term text of those documents */
+    uint64_t terms_probed;       /* ACGT document terms looked up in the negatives' table */
+    uint64_t negatives_removed;  /* candidates dropped because one of their terms occurs in a document */
+    double kernel_ms;            /* device time of the table build and the batches' kernels */
+} cobs_gpu_querygen_stats;
+
+/* Argument errors (term_size 0, more positives than terms, ...) come back before any device work.
+ * Fails with COBS_GPU_ERR_ARG when fewer than num_negative negatives survive, and with
+ * COBS_GPU_ERR_FORMAT naming the document when a drawn term index lies beyond the terms a document
+ * actually holds (its num_terms overstates them). */
+cobs_gpu_status cobs_gpu_generate_queries(const cobs_gpu_doclist* dl, const cobs_gpu_querygen_params* params,
+                                          cobs_gpu_query_set** out);
+size_t cobs_gpu_query_set_size(const cobs_gpu_query_set* set);
+/* entry i in output order: its sequence (owned by the set), its document (UINT64_MAX for a negative)
+ * and the term's index inside that document */
+cobs_gpu_status cobs_gpu_query_set_entry(const cobs_gpu_query_set* set, size_t i, const char** text, size_t* len,
+                                         uint64_t* doc_index, uint64_t* term_index);
+/* the reference's write_output: ">doc:D:term:T:NAME" or ">negativeI" lines, each followed by its
+ * sequence; dl names the documents (the list the set was generated from); path NULL = stdout */
+cobs_gpu_status cobs_gpu_query_set_write(const cobs_gpu_query_set* set, const cobs_gpu_doclist* dl, const char* path);
+cobs_gpu_status cobs_gpu_query_set_stats(const cobs_gpu_query_set* set, cobs_gpu_querygen_stats* out);
+void cobs_gpu_query_set_free(cobs_gpu_query_set* set);
+
 #ifdef __cplusplus
 }
 #endif

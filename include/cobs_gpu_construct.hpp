@@ -16,6 +16,7 @@
 //   void cobs::classic_construct_random(out_file, signature_size, num_documents,
 //                                       document_size, num_hashes, seed)            (classic_index.hpp:83-86)
 //   void cobs::compact_combine_into_compact(in_dir..., out_file, page_size)          (compact_index.hpp:56-60)
+//   `cobs generate-queries` as class QuerySet                                       (src/cobs.cpp:734-959)
 // Where the reference terminates the process (die / exit) these throw cobs_gpu::Error.  There is no
 // temporary directory (the matrix is built in HBM): tmp_path, mem_bytes, num_threads and
 // keep_temporary are accepted and unused.
@@ -221,5 +222,38 @@ inline void compact_combine_into_compact(const std::vector<std::string>& in_file
     for (const auto& f : in_files) cp.push_back(f.c_str());
     detail::check(cobs_gpu_combine_compact(cp.data(), cp.size(), out_file.c_str(), page_size));
 }
+
+//! `cobs generate-queries` (reference src/cobs.cpp:734-959): a labelled query set drawn from the list
+//! (see cobs_gpu_generate_queries; the random stream is the library's own, not the reference's)
+class QuerySet {
+public:
+    QuerySet(const DocumentList& list, const cobs_gpu_querygen_params& params) : list_(list.handle()) {
+        detail::check(cobs_gpu_generate_queries(list_, &params, &set_));
+    }
+    ~QuerySet() { cobs_gpu_query_set_free(set_); }
+    QuerySet(const QuerySet&) = delete;
+    QuerySet& operator=(const QuerySet&) = delete;
+    size_t size() const { return cobs_gpu_query_set_size(set_); }
+    //! doc_index is UINT64_MAX for a negative
+    std::string entry(size_t i, uint64_t* doc_index = nullptr, uint64_t* term_index = nullptr) const {
+        const char* t = nullptr;
+        size_t n = 0;
+        detail::check(cobs_gpu_query_set_entry(set_, i, &t, &n, doc_index, term_index));
+        return std::string(t, n);
+    }
+    //! the reference's output format; an empty path writes to stdout
+    void write(const std::string& path = std::string()) const {
+        detail::check(cobs_gpu_query_set_write(set_, list_, path.empty() ? nullptr : path.c_str()));
+    }
+    cobs_gpu_querygen_stats stats() const {
+        cobs_gpu_querygen_stats s;
+        detail::check(cobs_gpu_query_set_stats(set_, &s));
+        return s;
+    }
+
+private:
+    const cobs_gpu_doclist* list_;
+    cobs_gpu_query_set* set_ = nullptr;
+};
 
 }  // namespace cobs_gpu
