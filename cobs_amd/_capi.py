@@ -103,6 +103,8 @@ SYMBOLS = {
     "cobs_gpu_plant": (_int, [_vp, _sz, _cp, _sz, C.POINTER(_u32), C.POINTER(_u32), _sz, _u64]),
     "cobs_gpu_close": (None, [_vp]),
     "cobs_gpu_set_tuning": (_int, [_vp, _cp, C.c_int64]),
+    "cobs_gpu_set_findere": (_int, [_vp, _u32]),
+    "cobs_gpu_get_findere": (_int, [_vp, C.POINTER(_u32)]),
     "cobs_gpu_plan_shards": (_int, [_cp, _u32, _u32, _pu64, _pu64, _pu64]),
     "cobs_gpu_page_columns": (_int, [_vp, _sz, _u32, _pu64, _pu64]),
     "cobs_gpu_num_files": (_sz, [_vp]),
@@ -169,6 +171,8 @@ SYMBOLS = {
     "cobs_gpu_multi_close": (None, [_vp]),
     "cobs_gpu_multi_size": (_sz, [_vp]),
     "cobs_gpu_multi_index": (_vp, [_vp, _sz]),
+    "cobs_gpu_multi_set_findere": (_int, [_vp, _u32]),
+    "cobs_gpu_multi_get_findere": (_int, [_vp, C.POINTER(_u32)]),
     "cobs_gpu_multi_search_batch": (_int, [_vp, C.POINTER(_cp), C.POINTER(_sz), _sz, _dbl, _sz,
                                            C.POINTER(Hit), _sz, C.POINTER(_sz), C.POINTER(_sz)]),
     "cobs_gpu_graph_replays": (_u64, [_vp]),

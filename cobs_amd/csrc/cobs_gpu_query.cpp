@@ -9,6 +9,7 @@
 // sequence lines are concatenated.  Default threshold 0.8 (src/cobs.cpp:481-484).
 // Unlike the reference, which runs the queries of a file one after the other, the
 // whole file is one device batch.
+#include <algorithm>
 #include <cstdio>
 #include <unistd.h>
 #include <cstdlib>
@@ -28,7 +29,9 @@
 static void usage() {
     std::fprintf(stderr,
                  "usage: cobs_gpu_query -i INDEX [-i INDEX ...] [-t THRESHOLD] [-l LIMIT] "
-                 "[-d DEVICE[,DEVICE...]] [--hbm-budget GIB] (QUERY | -f QUERY_FILE)\n"
+                 "[-d DEVICE[,DEVICE...]] [--hbm-budget GIB] [--findere Z] (QUERY | -f QUERY_FILE)\n"
+                 "       --findere Z (0..7): a k-mer position scores only when Z + 1 consecutive k-mers are all present\n"
+                 "        (findere, beyond `cobs query`: far fewer false-positive k-mers; a query needs k + Z characters)\n"
                  "       -d 0,1,2,3: the index is sharded by sub-index block over the listed GPUs, every search is\n"
                  "        one scan per GPU + one RCCL exchange (same results as on one GPU)\n"
                  "       (--load-complete and -T/--threads of `cobs query` are accepted and ignored: the index\n"
@@ -39,8 +42,10 @@ static void usage() {
                  "                      [--file-type T] [--canonical] [-d DEVICE]   (`cobs generate-queries`, same flags)\n"
                  "       cobs_gpu_query --benchmark -i INDEX [-k KMERS] [-q QUERIES] [-w WARMUP] [--seed S] [--dist]\n"
                  "       cobs_gpu_query benchmark-fpr INDEX [-k KMERS] [-q QUERIES] [-w WARMUP] [-d|--dist] [--seed S] [--device N[,M..]]\n"
+                 "                      [--findere Z]\n"
                  "        (`cobs benchmark-fpr`, same flags: -d / --dist adds the distribution of all scores,\n"
-                 "         RESULT name=benchmark_fpr fpr=<score> dist=<count> lines)\n"
+                 "         RESULT name=benchmark_fpr fpr=<score> dist=<count> lines; --findere Z adds findere=Z and\n"
+                 "         fpr=<scoring positions / all positions of the timed queries in all documents> to the RESULT line)\n"
                  "       cobs_gpu_query --write-synthetic OUT (--classic -n DOCS -s ROWS | --compact -n DOCS -p PAGE_SIZE\n"
                  "                      -s ROWS_0,ROWS_1,...) [--num-hashes H] [--seed S] [-d DEVICE]\n"
                  "        (a random-bit index file, density 0.3, for benchmarks of any size)\n"
@@ -80,7 +85,7 @@ static bool score_distribution(const std::vector<cobs_gpu_index*>& shards, const
 }
 
 static int benchmark(cobs_gpu::BatchSearch& s, const std::string& index, unsigned num_kmers,
-                     unsigned num_queries, unsigned num_warmup, size_t seed, bool dist = false) {
+                     unsigned num_queries, unsigned num_warmup, size_t seed, bool dist = false, int findere = -1) {
     static const char basepairs[4] = {'A', 'C', 'G', 'T'};
     std::mt19937 rng(seed);
     auto make = [&](unsigned n) {
@@ -107,8 +112,22 @@ static int benchmark(cobs_gpu::BatchSearch& s, const std::string& index, unsigne
               << " t_hashes=" << t.get("hashes") << " t_io=" << t.get("io") << " t_and=" << t.get("and rows")
               << " t_add=" << t.get("add rows") << " t_sort=" << t.get("sort results") << " backend=gpu"
               << " t_scan=" << t.get("scan") << " t_h2d=" << t.get("h2d") << " t_d2h=" << t.get("d2h")
-              << " t_rank=" << t.get("rank") << " t_total=" << wall << " queries_per_s=" << num_queries / wall
-              << std::endl;
+              << " t_rank=" << t.get("rank") << " t_total=" << wall << " queries_per_s=" << num_queries / wall;
+    if (findere >= 0) {
+        // the false-positive rate of random queries: scoring positions over all positions (T_f - z per document of file f)
+        double scored = 0, positions = 0;
+        for (const auto& r : results)
+            for (const auto& h : r) scored += (double)h.score;
+        cobs_gpu_index* ix = s.handle();
+        for (size_t f = 0; f < cobs_gpu_num_files(ix); ++f) {
+            cobs_gpu_index_info in{};
+            if (cobs_gpu_info(ix, f, &in) != COBS_GPU_OK) continue;
+            const double T = (double)(num_kmers + 30) - (double)in.term_size + 1.0 - (double)findere;
+            positions += (double)num_queries * (double)in.num_docs * std::max(T, 0.0);
+        }
+        std::cout << " findere=" << findere << " fpr=" << (positions > 0 ? scored / positions : 0.0);
+    }
+    std::cout << std::endl;
     if (dist) {
         results.clear();
         results.shrink_to_fit();
@@ -154,6 +173,7 @@ int main(int argc, char** argv) {
     bool synth_compact = false, force_sharded = false;
     uint64_t synth_docs = 10000, synth_page = 0, synth_hashes = 1;
     bool bench = fpr_mode, dist = false;
+    int findere = -1;                        // --findere Z; -1: not given (the handle's default, 0)
     unsigned num_kmers = 1000, num_queries = 10000, num_warmup = 100;
     size_t seed = std::random_device{}();
     for (int i = 1; i < argc; ++i) {
@@ -194,6 +214,13 @@ int main(int argc, char** argv) {
         else if (a == "-q" || a == "--queries") num_queries = (unsigned)std::atoi(need("-q"));
         else if (a == "-w" || a == "--warmup") num_warmup = (unsigned)std::atoi(need("-w"));
         else if (a == "--seed") seed = (size_t)std::strtoull(need("--seed"), nullptr, 10);
+        else if (a == "--findere") {
+            const std::string v = need("--findere");
+            char* end = nullptr;
+            const long z = std::strtol(v.c_str(), &end, 10);
+            if (v.empty() || *end != '\0' || z < 0 || z > 7) { std::fprintf(stderr, "--findere: 0 .. 7\n"); return 1; }
+            findere = (int)z;
+        }
         else if (a == "-h" || a == "--help") { usage(); return 0; }
         else if (!a.empty() && a[0] == '-') { std::fprintf(stderr, "unknown flag %s\n", a.c_str()); usage(); return 1; }
         else if (fpr_mode && index_paths.empty()) index_paths.push_back(a);
@@ -209,10 +236,16 @@ int main(int argc, char** argv) {
             StdoutToStderr() { std::fflush(stdout); saved = dup(1); dup2(2, 1); }
             ~StdoutToStderr() { std::fflush(stdout); dup2(saved, 1); close(saved); }
         } quiet;
-        if (devices.size() > 1 || force_sharded)
-            return std::unique_ptr<cobs_gpu::BatchSearch>(new cobs_gpu::ShardedClassicSearch(
-                index_paths, devices.empty() ? std::vector<int>{0} : devices, hbm_budget));
-        return std::unique_ptr<cobs_gpu::BatchSearch>(new cobs_gpu::ClassicSearch(index_paths, device, hbm_budget));
+        if (devices.size() > 1 || force_sharded) {
+            auto* sh = new cobs_gpu::ShardedClassicSearch(index_paths, devices.empty() ? std::vector<int>{0} : devices, hbm_budget);
+            std::unique_ptr<cobs_gpu::BatchSearch> keep(sh);
+            if (findere > 0) sh->set_findere((unsigned)findere);
+            return keep;
+        }
+        auto* cs = new cobs_gpu::ClassicSearch(index_paths, device, hbm_budget);
+        std::unique_ptr<cobs_gpu::BatchSearch> keep(cs);
+        if (findere > 0) cs->set_findere((unsigned)findere);
+        return keep;
     };
     if (!random_out.empty()) {
         // `cobs classic-construct-random` (reference src/cobs.cpp:243-291): same flags and defaults
@@ -252,7 +285,7 @@ int main(int argc, char** argv) {
         try {
             std::unique_ptr<cobs_gpu::BatchSearch> sp = open_index();
             cobs_gpu::BatchSearch& s = *sp;
-            return benchmark(s, index_paths[0], num_kmers, num_queries, num_warmup, seed, dist);
+            return benchmark(s, index_paths[0], num_kmers, num_queries, num_warmup, seed, dist, findere);
         } catch (const cobs_gpu::Error& e) {
             std::fprintf(stderr, "EXCEPTION: %s\n", e.what());
             return 1;

@@ -611,6 +611,25 @@ cobs_gpu_status cobs_gpu_set_tuning(cobs_gpu_index* ix, const char* key, int64_t
     return COBS_GPU_OK;
 }
 
+cobs_gpu_status cobs_gpu_set_findere(cobs_gpu_index* ix, uint32_t z) {
+    if (!ix) return fail(COBS_GPU_ERR_ARG, "NULL argument");
+    if (z > 7u) return fail(COBS_GPU_ERR_ARG, "findere: z is 0 .. 7");
+    if (z > 0u) {
+        // a streamed file counts row ranges separately: no per-position presence to AND over the window
+        bool streamed = ix->hbm_budget != 0;
+        for (const Part& p : ix->parts) streamed = streamed || p.streamed;
+        if (streamed) return fail(COBS_GPU_ERR_UNSUPPORTED, "findere: not on a handle with an HBM budget (streamed files)");
+    }
+    ix->findere = z;
+    return COBS_GPU_OK;
+}
+
+cobs_gpu_status cobs_gpu_get_findere(const cobs_gpu_index* ix, uint32_t* z) {
+    if (!ix || !z) return fail(COBS_GPU_ERR_ARG, "NULL argument");
+    *z = ix->findere;
+    return COBS_GPU_OK;
+}
+
 size_t cobs_gpu_num_files(const cobs_gpu_index* ix) { return ix ? ix->parts.size() : 0; }
 
 cobs_gpu_status cobs_gpu_info(const cobs_gpu_index* ix, size_t f, cobs_gpu_index_info* o) {

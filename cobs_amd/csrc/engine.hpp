@@ -267,6 +267,7 @@ struct cobs_gpu_index {
     uint32_t shard_rank = 0, shard_count = 1, shard_mode = 0;
     uint64_t hbm_budget = 0;      // 0 = everything resident
     uint32_t waves_per_group = 0; // 0 = by query length
+    uint32_t findere = 0;         // cobs_gpu_set_findere: z (0..7); every batch samples it when it runs
     cobs_amd::Tuning tune;
     std::vector<cobs_amd::Part> parts;
     cobs_amd::StreamBufs stream;
@@ -302,6 +303,7 @@ struct cobs_gpu_batch {
     uint32_t elem_bytes = 2;
     int planes = 0;
     uint64_t max_terms = 0;              // longest query of the batch, in terms
+    uint32_t findere = 0;                // z of the current / last run (the handle's, sampled by set_run_state)
     cobs_amd::DevBuf<cobs_amd::HitDev> hits;
     cobs_amd::DevBuf<uint2> topk_out;    // K3 output [file][query][k], ordered (score desc, doc asc)
     cobs_amd::DevBuf<uint32_t> topk_cnt; // [file][query]
@@ -450,6 +452,10 @@ cobs_gpu_status set_queries_on(cobs_gpu_batch* b, const char* const* queries, co
                                hipStream_t up, bool wait, size_t* bad_query, size_t index_base = 0);
 uint32_t threshold_for(double threshold, uint64_t terms);
 uint64_t total_hashes(const cobs_gpu_batch* b, size_t q);
+// positions query q scores in file p: its terms T = |q| - k + 1, less the batch's findere z (windows of z + 1 terms)
+uint64_t scored_positions(const cobs_gpu_batch* b, size_t q, const Part& p);
+// QUERY_TOO_SHORT unless every query of the batch has a window in every file (|q| >= k + z)
+cobs_gpu_status check_findere_lengths(const cobs_gpu_batch* b, size_t index_base = 0);
 bool hit_before(const cobs_gpu_hit& a, const cobs_gpu_hit& b);
 bool doc_before(const cobs_gpu_hit& a, const cobs_gpu_hit& b);
 void destroy_exchange(Exchange* x);       // comm.cpp

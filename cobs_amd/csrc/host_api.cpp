@@ -68,6 +68,7 @@ static cobs_gpu_status host_pass_begin(cobs_gpu_index* ix, int slot, const char*
     bool any_streamed = false;
     for (const auto& p : ix->parts) any_streamed = any_streamed || p.streamed;
     if (nq > 0 && nq <= 16 && ix->tune.graph != 0 && !any_streamed && !ix->tune.phase_slots) {
+        b->findere = ix->findere;            // (the shape class holds it; run_impl samples the same)
         // the shape class of the pass and every address the captured nodes hold
         auto make_key = [&]() {
             uint64_t key = 1469598103934665603ull;

@@ -471,6 +471,52 @@ __device__ __forceinline__ void and_rows(uint4 (&X)[8], const uint4 (&Y)[8]) {
     }
 }
 
+// ---- findere (FZ instantiations of K2): a position counts only when the z + 1 consecutive terms of its window are all
+// present.  Per document a saturating DEFICIT d = max(z - run, 0), run = present terms in a row up to here, bit-sliced
+// in three planes (z <= 7) per column word: the window ending at term i is complete iff P_i and d_{i-1} == 0; then
+// d_i = P_i ? max(d_{i-1} - 1, 0) : z.  Eight VALU per column word and term (v_bitop3), 12 VGPRs of state per lane.
+// d starts at z: terms before position 0 are absent.
+struct FzState {
+    uint32_t d0[4], d1[4], d2[4];       // deficit planes of the lane's 4 column words
+    uint32_t z0, z1, z2;                // z as all-zero / all-one masks per bit (wave-uniform)
+};
+
+__device__ __forceinline__ void fz_init(FzState& s, uint32_t z) {
+    s.z0 = (z & 1u) ? ~0u : 0u;
+    s.z1 = (z & 2u) ? ~0u : 0u;
+    s.z2 = (z & 4u) ? ~0u : 0u;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) { s.d0[w] = s.z0; s.d1[w] = s.z1; s.d2[w] = s.z2; }
+}
+
+// one term's presence word p of column word w -> its window word
+__device__ __forceinline__ uint32_t fz_step(FzState& s, int w, uint32_t p) {
+    const uint32_t d0 = s.d0[w], d1 = s.d1[w], d2 = s.d2[w];
+    const uint32_t nz = __builtin_amdgcn_bitop3_b32(d0, d1, d2, 0xFE);      // d != 0
+    const uint32_t win = __builtin_amdgcn_bitop3_b32(p, nz, nz, 0x30);      // p & ~nz
+    // d - 1 saturating at 0: bit 0 = ~d0 & (d1 | d2), bit 1 = d1 ^ (~d0 & (d1 | d2)), bit 2 = d2 & (d0 | d1)
+    const uint32_t e0 = __builtin_amdgcn_bitop3_b32(d0, d1, d2, 0x0E);
+    const uint32_t e1 = __builtin_amdgcn_bitop3_b32(d0, d1, d2, 0xC2);
+    const uint32_t e2 = __builtin_amdgcn_bitop3_b32(d0, d1, d2, 0xA8);
+    // present: decremented; absent: z (select p ? e : z)
+    s.d0[w] = __builtin_amdgcn_bitop3_b32(p, e0, s.z0, 0xCA);
+    s.d1[w] = __builtin_amdgcn_bitop3_b32(p, e1, s.z1, 0xCA);
+    s.d2[w] = __builtin_amdgcn_bitop3_b32(p, e2, s.z2, 0xCA);
+    return win;
+}
+
+// N consecutive terms (in query order) of presence words -> window words, in place
+template <int N>
+__device__ __forceinline__ void fz_window(FzState& s, uint4 (&X)[N]) {
+#pragma unroll
+    for (int t = 0; t < N; ++t) {
+        X[t].x = fz_step(s, 0, X[t].x);
+        X[t].y = fz_step(s, 1, X[t].y);
+        X[t].z = fz_step(s, 2, X[t].z);
+        X[t].w = fz_step(s, 3, X[t].w);
+    }
+}
+
 // ---- LDS-staged variant of the row pipeline (LDSS): rows travel HBM -> LDS (direct-to-LDS DMA,
 // global_load_lds_dwordx4: 64 lanes x 16 B = 1 KiB per instruction) -> VGPR (ds_read_b128)
 // instead of HBM -> VGPR.  hipcc neither counts asm memory operations nor pipelines LDS-DMA
@@ -724,8 +770,12 @@ __device__ __forceinline__ void tile_topk(const ScanArgs& a, const uint32_t (&pl
 // kernels whose epilogue they replace: the selection's masks would otherwise cost the multi-query ones a wave;
 // so are the generic-H instantiations of one and two waves per group, whose half-block row loop fits them -- the
 // four-wave one would spill in that loop and is left to the compiler: geometry.cpp does not choose it)
-template <int NP, int NW, bool H1, typename OutT, bool MQ, typename IdxT, bool LDSS = false, bool TK = false>
-__global__ __launch_bounds__(NW * 64, (((TK && H1) || (!H1 && sizeof(IdxT) == 4 && !LDSS && (NW <= 2 || TK))) && NP <= 10) ? 4 : 1) void scan_kernel(ScanArgs a) {
+// FZ: findere (ScanArgs::findere = z > 0) -- every term's presence words become window words (fz_window) before the
+// counter tree, and a virtual wave walks a CONTIGUOUS range of the query's blocks, primed with the z terms in front of
+// it (loaded, not counted).  Left to the compiler's register budget (the deficit planes cost 12 VGPRs).
+template <int NP, int NW, bool H1, typename OutT, bool MQ, typename IdxT, bool LDSS = false, bool TK = false, bool FZ = false>
+__global__ __launch_bounds__(NW * 64, (!FZ && ((TK && H1) || (!H1 && sizeof(IdxT) == 4 && !LDSS && (NW <= 2 || TK))) && NP <= 10) ? 4 : 1) void scan_kernel(ScanArgs a) {
+    static_assert(!(FZ && LDSS), "findere: no LDS-staged variant");
     // row loads stay temporal: non-temporal loads measured 18 % slower (they bypass the Infinity Cache)
     constexpr bool NT = false;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -801,9 +851,12 @@ __global__ __launch_bounds__(NW * 64, (((TK && H1) || (!H1 && sizeof(IdxT) == 4 
                       ((b0 + q) * a.table_npages + (uint64_t)pdl.tpage * (nblk_q + 1u)) * (8ull * H);
     const uint32_t vw = MQ ? wave : wave * G + grp;  // virtual wave of this lane
     const uint32_t NV = MQ ? (uint32_t)NW : NW * G;
-    // block of this lane in trip i: vw + i * NV, or the padding block when it has run out
+    // findere: blocks [fz_first, fz_first + fz_per) of the query (a sliding window needs its terms in order)
+    const uint32_t fz_per = FZ ? (nblk + NV - 1u) / NV : 0u;
+    const uint32_t fz_first = FZ ? vw * fz_per : 0u;
+    // block of this lane in trip i: vw + i * NV (findere: fz_first + i), or the padding block when it has run out
     auto blk_of = [&](uint32_t i) -> uint64_t {
-        const uint32_t bidx = vw + i * NV;
+        const uint32_t bidx = FZ ? (i < fz_per ? fz_first + i : nblk) : vw + i * NV;
         return (uint64_t)(bidx < nblk ? bidx : nblk_q) * 8u * H;
     };
 
@@ -817,15 +870,38 @@ __global__ __launch_bounds__(NW * 64, (((TK && H1) || (!H1 && sizeof(IdxT) == 4 
     uint32_t nw;
     if constexpr (MQ) {
         // the longest query among the wave's lane groups sets the trip count
-        uint32_t need = nblk > wave ? (nblk - wave + NW - 1u) / NW : 0u;
+        uint32_t need = FZ ? (nblk > fz_first ? min(nblk - fz_first, fz_per) : 0u)
+                           : nblk > wave ? (nblk - wave + NW - 1u) / NW : 0u;
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) need = max(need, (uint32_t)__shfl_xor(need, off));
         nw = __builtin_amdgcn_readfirstlane(need);
+    } else if constexpr (FZ) {
+        // the wave's first lane group has the first (and longest) of its ranges
+        const uint32_t first = wave * G * fz_per;
+        nw = __builtin_amdgcn_readfirstlane(nblk > first ? min(nblk - first, fz_per) : 0u);
     } else {
         const uint32_t first = wave * G;
         nw = nblk > first ? (nblk - first + NV - 1u) / NV : 0u;
     }
     uint32_t ea[4], eb[4];
+    FzState fz;
+    if constexpr (FZ) {
+        fz_init(fz, a.findere);
+        // prime the deficit with the z terms in front of the range: the last z terms of block fz_first - 1
+        // (z <= 7 < 8), loaded and not counted; the deficit after them does not depend on what came before
+        if (fz_first > 0u && fz_first < nblk) {
+            const IdxT* pt = tab + (uint64_t)(fz_first - 1u) * 8u * H;
+            for (uint32_t t = 8u - a.findere; t < 8u; ++t) {
+                uint4 P[1];
+                P[0] = load_row<NT>(lane_base, (uint64_t)pt[t], pitch);
+                for (uint32_t j = 1; j < H; ++j) {
+                    const uint4 r = load_row<NT>(lane_base, (uint64_t)pt[8u * j + t], pitch);
+                    P[0].x &= r.x; P[0].y &= r.y; P[0].z &= r.z; P[0].w &= r.w;
+                }
+                fz_window<1>(fz, P);
+            }
+        }
+    }
     COBS_STAMP(1);                 // page / block-offset loads done, LUT written
     if constexpr (LDSS) {
         static_assert(!LDSS || (H1 && !MQ && sizeof(IdxT) == 4), "LDS-staged variant: H = 1, one query per group, 32-bit indices");
@@ -901,19 +977,24 @@ __global__ __launch_bounds__(NW * 64, (((TK && H1) || (!H1 && sizeof(IdxT) == 4 
                 // XA in flight = trip i, i1 = indices of trip i+1
                 i0 = load_idx8(tab + blk_of(i + 2));
                 issue_rows<NT>(XB, lane_base, pitch, i1);
+                if constexpr (FZ) fz_window<8>(fz, XA);
                 absorb_block<NP>(pl, XA, ea);
                 i1 = load_idx8(tab + blk_of(i + 3));
                 issue_rows<NT>(XA, lane_base, pitch, i0);
+                if constexpr (FZ) fz_window<8>(fz, XB);
                 absorb_block<NP>(pl, XB, eb);
                 retire_pair<NP>(pl, ea, eb);
             }
             // XA in flight = trip i; one or two trips left
             if (i + 1 < nw) {
                 issue_rows<NT>(XB, lane_base, pitch, i1);
+                if constexpr (FZ) fz_window<8>(fz, XA);
                 absorb_block<NP>(pl, XA, ea);
+                if constexpr (FZ) fz_window<8>(fz, XB);
                 absorb_block<NP>(pl, XB, eb);
                 retire_pair<NP>(pl, ea, eb);
             } else {
+                if constexpr (FZ) fz_window<8>(fz, XA);
                 absorb_block<NP>(pl, XA, ea);
                 retire_single<NP>(pl, ea);
             }
@@ -948,6 +1029,7 @@ __global__ __launch_bounds__(NW * 64, (((TK && H1) || (!H1 && sizeof(IdxT) == 4 
                 }
                 if (++cj == H) {
                     cj = 0;
+                    if constexpr (FZ) fz_window<4>(fz, ACC);
                     const uint32_t g0 = absorb4<NP>(pl[0], ACC[0].x, ACC[1].x, ACC[2].x, ACC[3].x);
                     const uint32_t g1 = absorb4<NP>(pl[1], ACC[0].y, ACC[1].y, ACC[2].y, ACC[3].y);
                     const uint32_t g2 = absorb4<NP>(pl[2], ACC[0].z, ACC[1].z, ACC[2].z, ACC[3].z);
@@ -1008,6 +1090,7 @@ __global__ __launch_bounds__(NW * 64, (((TK && H1) || (!H1 && sizeof(IdxT) == 4 
                 }
                 if (++cj == H) {
                     cj = 0;
+                    if constexpr (FZ) fz_window<8>(fz, ACC);
                     absorb_block<NP>(pl, ACC, ea);
                     retire_single<NP>(pl, ea);
                 }
@@ -1984,7 +2067,8 @@ hipError_t launch_hash(const HashArgs& a, uint64_t total_threads, hipStream_t st
     return hipGetLastError();
 }
 
-template <int NP, int NW, bool H1, typename OutT, bool MQ = false, typename IdxT = uint32_t, bool LDSS = false, bool TK = false>
+template <int NP, int NW, bool H1, typename OutT, bool MQ = false, typename IdxT = uint32_t, bool LDSS = false, bool TK = false,
+          bool FZ = false>
 static hipError_t launch_scan_inst(const ScanArgs& a, uint32_t ntiles, hipStream_t stream) {
     (void)ntiles;
     const uint32_t per_group = MQ ? 64u / a.tile_w : 1u;
@@ -1994,7 +2078,7 @@ static hipError_t launch_scan_inst(const ScanArgs& a, uint32_t ntiles, hipStream
     if (groups > 0x7FFFFFFFull) return hipErrorInvalidValue;
     constexpr size_t front = scan_lds_front<NP, NW, sizeof(OutT), LDSS>();
     constexpr size_t lds = front + (sizeof(OutT) == 1 ? 0 : 256 * sizeof(uint4)) + 64 * 4 * sizeof(uint32_t);
-    auto kern = scan_kernel<NP, NW, H1, OutT, MQ, IdxT, LDSS, TK>;
+    auto kern = scan_kernel<NP, NW, H1, OutT, MQ, IdxT, LDSS, TK, FZ>;
     if (lds > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -2005,43 +2089,43 @@ static hipError_t launch_scan_inst(const ScanArgs& a, uint32_t ntiles, hipStream
 }
 
 // multi-query variant: H = 1, u16 scores (short queries)
-template <int NP, typename OutT>
+template <int NP, typename OutT, bool FZ>
 static hipError_t launch_scan_mq(const ScanArgs& a, uint32_t ntiles, int nw, hipStream_t stream) {
     if (a.cand) {           // run_topk without score rows
-        if (nw == 1) return launch_scan_inst<NP, 1, true, OutT, true, uint32_t, false, true>(a, ntiles, stream);
-        if (nw == 2) return launch_scan_inst<NP, 2, true, OutT, true, uint32_t, false, true>(a, ntiles, stream);
-        return launch_scan_inst<NP, 4, true, OutT, true, uint32_t, false, true>(a, ntiles, stream);
+        if (nw == 1) return launch_scan_inst<NP, 1, true, OutT, true, uint32_t, false, true, FZ>(a, ntiles, stream);
+        if (nw == 2) return launch_scan_inst<NP, 2, true, OutT, true, uint32_t, false, true, FZ>(a, ntiles, stream);
+        return launch_scan_inst<NP, 4, true, OutT, true, uint32_t, false, true, FZ>(a, ntiles, stream);
     }
-    if (nw == 1) return launch_scan_inst<NP, 1, true, OutT, true>(a, ntiles, stream);
-    if (nw == 2) return launch_scan_inst<NP, 2, true, OutT, true>(a, ntiles, stream);
-    return launch_scan_inst<NP, 4, true, OutT, true>(a, ntiles, stream);
+    if (nw == 1) return launch_scan_inst<NP, 1, true, OutT, true, uint32_t, false, false, FZ>(a, ntiles, stream);
+    if (nw == 2) return launch_scan_inst<NP, 2, true, OutT, true, uint32_t, false, false, FZ>(a, ntiles, stream);
+    return launch_scan_inst<NP, 4, true, OutT, true, uint32_t, false, false, FZ>(a, ntiles, stream);
 }
 
-template <int NP, typename OutT>
+template <int NP, typename OutT, bool FZ>
 static hipError_t launch_scan_np(const ScanArgs& a, uint32_t ntiles, bool h1, int nw, hipStream_t stream) {
     if (a.cand) {           // run_topk without score rows: 32-bit row indices (scan_has_tile_topk)
         if (a.idx64) return hipErrorInvalidValue;
-        if (nw == 1) return h1 ? launch_scan_inst<NP, 1, true, OutT, false, uint32_t, false, true>(a, ntiles, stream)
-                               : launch_scan_inst<NP, 1, false, OutT, false, uint32_t, false, true>(a, ntiles, stream);
-        if (nw == 2) return h1 ? launch_scan_inst<NP, 2, true, OutT, false, uint32_t, false, true>(a, ntiles, stream)
-                               : launch_scan_inst<NP, 2, false, OutT, false, uint32_t, false, true>(a, ntiles, stream);
-        return h1 ? launch_scan_inst<NP, 4, true, OutT, false, uint32_t, false, true>(a, ntiles, stream)
-                  : launch_scan_inst<NP, 4, false, OutT, false, uint32_t, false, true>(a, ntiles, stream);
+        if (nw == 1) return h1 ? launch_scan_inst<NP, 1, true, OutT, false, uint32_t, false, true, FZ>(a, ntiles, stream)
+                               : launch_scan_inst<NP, 1, false, OutT, false, uint32_t, false, true, FZ>(a, ntiles, stream);
+        if (nw == 2) return h1 ? launch_scan_inst<NP, 2, true, OutT, false, uint32_t, false, true, FZ>(a, ntiles, stream)
+                               : launch_scan_inst<NP, 2, false, OutT, false, uint32_t, false, true, FZ>(a, ntiles, stream);
+        return h1 ? launch_scan_inst<NP, 4, true, OutT, false, uint32_t, false, true, FZ>(a, ntiles, stream)
+                  : launch_scan_inst<NP, 4, false, OutT, false, uint32_t, false, true, FZ>(a, ntiles, stream);
     }
     if (a.idx64) {
         // sub-indexes with >= 2^32 rows: 64-bit row indices; two waves per group cover every
         // query length well enough for this rare geometry (keeps the instantiation count down)
-        return h1 ? launch_scan_inst<NP, 2, true, OutT, false, uint64_t>(a, ntiles, stream)
-                  : launch_scan_inst<NP, 2, false, OutT, false, uint64_t>(a, ntiles, stream);
+        return h1 ? launch_scan_inst<NP, 2, true, OutT, false, uint64_t, false, false, FZ>(a, ntiles, stream)
+                  : launch_scan_inst<NP, 2, false, OutT, false, uint64_t, false, false, FZ>(a, ntiles, stream);
     }
     if (nw == 1)
-        return h1 ? launch_scan_inst<NP, 1, true, OutT>(a, ntiles, stream)
-                  : launch_scan_inst<NP, 1, false, OutT>(a, ntiles, stream);
+        return h1 ? launch_scan_inst<NP, 1, true, OutT, false, uint32_t, false, false, FZ>(a, ntiles, stream)
+                  : launch_scan_inst<NP, 1, false, OutT, false, uint32_t, false, false, FZ>(a, ntiles, stream);
     if (nw == 2)
-        return h1 ? launch_scan_inst<NP, 2, true, OutT>(a, ntiles, stream)
-                  : launch_scan_inst<NP, 2, false, OutT>(a, ntiles, stream);
-    return h1 ? launch_scan_inst<NP, 4, true, OutT>(a, ntiles, stream)
-              : launch_scan_inst<NP, 4, false, OutT>(a, ntiles, stream);
+        return h1 ? launch_scan_inst<NP, 2, true, OutT, false, uint32_t, false, false, FZ>(a, ntiles, stream)
+                  : launch_scan_inst<NP, 2, false, OutT, false, uint32_t, false, false, FZ>(a, ntiles, stream);
+    return h1 ? launch_scan_inst<NP, 4, true, OutT, false, uint32_t, false, false, FZ>(a, ntiles, stream)
+              : launch_scan_inst<NP, 4, false, OutT, false, uint32_t, false, false, FZ>(a, ntiles, stream);
 }
 
 int scan_planes_for(uint64_t max_terms) {
@@ -2063,35 +2147,43 @@ bool scan_has_lds_staged(int planes, uint32_t num_hashes, int nw) {
     return num_hashes == 1 && planes == 10 && (nw == 2 || nw == 4);
 }
 
+template <bool FZ>
+static hipError_t launch_scan_fz(const ScanArgs& a, uint32_t ntiles, int planes, int nw, bool multi_query, hipStream_t stream) {
+    const bool h1 = a.num_hashes == 1;
+    if (multi_query) {
+        if (a.idx64 || !scan_has_multi_query(planes, a.num_hashes, a.tile_w)) return hipErrorInvalidValue;
+        switch (planes) {
+        case 4: return launch_scan_mq<4, uint8_t, FZ>(a, ntiles, nw, stream);
+        case 8: return launch_scan_mq<8, uint8_t, FZ>(a, ntiles, nw, stream);
+        case 10: return launch_scan_mq<10, uint16_t, FZ>(a, ntiles, nw, stream);
+        default: return launch_scan_mq<12, uint16_t, FZ>(a, ntiles, nw, stream);
+        }
+    }
+    switch (planes) {
+    case 4: return launch_scan_np<4, uint8_t, FZ>(a, ntiles, h1, nw, stream);
+    case 8: return launch_scan_np<8, uint8_t, FZ>(a, ntiles, h1, nw, stream);
+    case 10: return launch_scan_np<10, uint16_t, FZ>(a, ntiles, h1, nw, stream);
+    case 12: return launch_scan_np<12, uint16_t, FZ>(a, ntiles, h1, nw, stream);
+    case 16: return launch_scan_np<16, uint16_t, FZ>(a, ntiles, h1, nw, stream);
+    case 20: return launch_scan_np<20, uint32_t, FZ>(a, ntiles, h1, nw, stream);
+    case 24: return launch_scan_np<24, uint32_t, FZ>(a, ntiles, h1, nw, stream);
+    case 32: return launch_scan_np<32, uint32_t, FZ>(a, ntiles, h1, nw, stream);
+    default: return hipErrorInvalidValue;
+    }
+}
+
 hipError_t launch_scan(const ScanArgs& a, uint32_t ntiles, int planes, int nw, bool multi_query,
                        hipStream_t stream) {
-    const bool h1 = a.num_hashes == 1;
     if (a.cand && (a.lds_staged || a.topk_k == 0 || !scan_has_tile_topk(a.num_hashes, a.idx64 != 0))) return hipErrorInvalidValue;
+    if (a.findere > 7u || (a.findere && a.lds_staged)) return hipErrorInvalidValue;
     if (a.lds_staged) {     // measured variant (A/B): rows through LDS
         if (multi_query || a.idx64 || !scan_has_lds_staged(planes, a.num_hashes, nw)) return hipErrorInvalidValue;
         return nw == 2 ? launch_scan_inst<10, 2, true, uint16_t, false, uint32_t, true>(a, ntiles, stream)
                        : launch_scan_inst<10, 4, true, uint16_t, false, uint32_t, true>(a, ntiles, stream);
     }
-    if (multi_query) {
-        if (a.idx64 || !scan_has_multi_query(planes, a.num_hashes, a.tile_w)) return hipErrorInvalidValue;
-        switch (planes) {
-        case 4: return launch_scan_mq<4, uint8_t>(a, ntiles, nw, stream);
-        case 8: return launch_scan_mq<8, uint8_t>(a, ntiles, nw, stream);
-        case 10: return launch_scan_mq<10, uint16_t>(a, ntiles, nw, stream);
-        default: return launch_scan_mq<12, uint16_t>(a, ntiles, nw, stream);
-        }
-    }
-    switch (planes) {
-    case 4: return launch_scan_np<4, uint8_t>(a, ntiles, h1, nw, stream);
-    case 8: return launch_scan_np<8, uint8_t>(a, ntiles, h1, nw, stream);
-    case 10: return launch_scan_np<10, uint16_t>(a, ntiles, h1, nw, stream);
-    case 12: return launch_scan_np<12, uint16_t>(a, ntiles, h1, nw, stream);
-    case 16: return launch_scan_np<16, uint16_t>(a, ntiles, h1, nw, stream);
-    case 20: return launch_scan_np<20, uint32_t>(a, ntiles, h1, nw, stream);
-    case 24: return launch_scan_np<24, uint32_t>(a, ntiles, h1, nw, stream);
-    case 32: return launch_scan_np<32, uint32_t>(a, ntiles, h1, nw, stream);
-    default: return hipErrorInvalidValue;
-    }
+    // findere: its own instantiations, so that z = 0 launches exactly the plain kernels
+    return a.findere ? launch_scan_fz<true>(a, ntiles, planes, nw, multi_query, stream)
+                     : launch_scan_fz<false>(a, ntiles, planes, nw, multi_query, stream);
 }
 
 hipError_t launch_topk(const TopkArgs& a, hipStream_t stream) {

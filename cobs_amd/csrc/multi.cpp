@@ -198,6 +198,25 @@ cobs_gpu_index* cobs_gpu_multi_index(const cobs_gpu_multi* m, size_t rank) {
     return m && rank < m->ranks.size() ? m->ranks[rank].ix : nullptr;
 }
 
+cobs_gpu_status cobs_gpu_multi_set_findere(cobs_gpu_multi* m, uint32_t z) {
+    if (!m || m->ranks.empty()) return fail(COBS_GPU_ERR_ARG, "NULL argument");
+    // every shard applies the same z: check them all before changing any
+    for (const auto& r : m->ranks) {
+        uint32_t old = 0;
+        if (cobs_gpu_status s = cobs_gpu_get_findere(r.ix, &old); s != COBS_GPU_OK) return s;
+        if (cobs_gpu_status s = cobs_gpu_set_findere(r.ix, z); s != COBS_GPU_OK) return s;
+        (void)cobs_gpu_set_findere(r.ix, old);
+    }
+    for (const auto& r : m->ranks)
+        if (cobs_gpu_status s = cobs_gpu_set_findere(r.ix, z); s != COBS_GPU_OK) return s;
+    return COBS_GPU_OK;
+}
+
+cobs_gpu_status cobs_gpu_multi_get_findere(const cobs_gpu_multi* m, uint32_t* z) {
+    if (!m || m->ranks.empty()) return fail(COBS_GPU_ERR_ARG, "NULL argument");
+    return cobs_gpu_get_findere(m->ranks[0].ix, z);
+}
+
 cobs_gpu_status cobs_gpu_multi_search_batch(cobs_gpu_multi* m, const char* const* queries, const size_t* lens, size_t nq,
                                             double threshold, size_t num_results, cobs_gpu_hit* hits, size_t cap,
                                             size_t* hit_offsets, size_t* bad_query) {

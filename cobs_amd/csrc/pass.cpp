@@ -30,12 +30,28 @@ uint64_t gathered_row_bytes(const Part& p) {
 }
 
 
-// total number of hashes of query `q` over all files: the reference's max_counts
+uint64_t scored_positions(const cobs_gpu_batch* b, size_t q, const Part& p) {
+    return (uint64_t)b->lens[q] - p.meta.term_size + 1 - b->findere;
+}
+
+// total number of hashes of query `q` over all files: the reference's max_counts (findere: (T - z) * H)
 uint64_t total_hashes(const cobs_gpu_batch* b, size_t q) {
     uint64_t n = 0;
     for (const Part& p : b->ix->parts)
-        n += (uint64_t)(b->lens[q] - p.meta.term_size + 1) * p.meta.num_hashes;
+        n += scored_positions(b, q, p) * p.meta.num_hashes;
     return n;
+}
+
+cobs_gpu_status check_findere_lengths(const cobs_gpu_batch* b, size_t index_base) {
+    if (b->findere == 0) return COBS_GPU_OK;
+    uint32_t max_term = 0;
+    for (const Part& p : b->ix->parts) max_term = std::max(max_term, p.meta.term_size);
+    for (size_t q = 0; q < b->nq; ++q)
+        if ((uint64_t)b->lens[q] < (uint64_t)max_term + b->findere)
+            return fail(COBS_GPU_ERR_QUERY_TOO_SHORT, "query too short, needs to be at least " +
+                        std::to_string(max_term + b->findere) + " characters long with findere z = " +
+                        std::to_string(b->findere) + " (query " + std::to_string(index_base + q) + ")");
+    return COBS_GPU_OK;
 }
 
 uint32_t threshold_for(double threshold, uint64_t terms) {
@@ -89,6 +105,7 @@ cobs_gpu_status cobs_amd::set_queries_on(cobs_gpu_batch* b, const char* const* q
     if (b->ran && !b->synced) HIP_TRY(hipEventSynchronize(b->run_done));
     b->ran = false;
     b->nq = 0;
+    b->findere = ix->findere;         // (run_impl samples it again: a batch runs with the z of its handle at that time)
     if (nq >= 0xFFFFFFFEull) return fail(COBS_GPU_ERR_ARG, "too many queries");
     // reference checks, classic_search.cpp:431-433 and :453-504
     uint32_t max_term = 0, min_term = 0xFFFFFFFFu;
@@ -100,9 +117,11 @@ cobs_gpu_status cobs_amd::set_queries_on(cobs_gpu_batch* b, const char* const* q
     for (size_t q = 0; q < nq; ++q) {
         if (bad_query) *bad_query = q;
         if (!queries[q]) return fail(COBS_GPU_ERR_ARG, "NULL query (query " + std::to_string(index_base + q) + ")");
-        if (lens[q] < max_term)
+        if (lens[q] < max_term + ix->findere)
             return fail(COBS_GPU_ERR_QUERY_TOO_SHORT, "query too short, needs to be at least " +
-                        std::to_string(max_term) + " characters long (query " + std::to_string(index_base + q) + ")");
+                        std::to_string(max_term + ix->findere) + " characters long" +
+                        (ix->findere ? " with findere z = " + std::to_string(ix->findere) : std::string()) +
+                        " (query " + std::to_string(index_base + q) + ")");
         if (lens[q] - max_term >= 0xFFFFFFFFull || lens[q] >= 0xFFFFFFF0ull)
             return fail(COBS_GPU_ERR_QUERY_TOO_LONG, "query too long (query " + std::to_string(index_base + q) + ")");
         max_terms = std::max<uint64_t>(max_terms, lens[q] - min_term + 1);
@@ -217,6 +236,7 @@ uint64_t cobs_amd::pass_shape_class(const cobs_gpu_batch* b) {
     bool single = false;
     for (size_t q = 0; q < nq && !single; ++q) single = total_hashes(b, q) <= 1;
     mixin(single);
+    mixin(b->findere);             // a kernel argument of the captured scan (and its instantiation)
     for (size_t f = 0; f < ix->parts.size() && nq; ++f) {
         const Part& p = ix->parts[f];
         for (const Chunk& c : p.chunks) {
@@ -242,6 +262,7 @@ void cobs_amd::set_run_state(cobs_gpu_batch* b, double threshold, size_t topk, b
     b->topk_stride = 0;
     b->graph_run = false;
     b->threshold = threshold;
+    b->findere = ix->findere;
     // K3 (exact top-k on the device, every score width) needs a bounded k
     const bool use_topk = topk > 0 && topk <= 65536 &&
                           (uint64_t)topk * std::max<size_t>(b->nq, 1) * ix->parts.size() <= (1ull << 27);
@@ -276,7 +297,7 @@ void cobs_amd::stage_thresholds(cobs_gpu_batch* b, double threshold) {
     for (size_t f = 0; f < ix->parts.size(); ++f) {
         uint32_t* stage = b->h_thr_stage.p + f * nq;
         for (size_t q = 0; q < nq; ++q)
-            stage[q] = threshold_for(threshold, (uint64_t)b->lens[q] - ix->parts[f].meta.term_size + 1);
+            stage[q] = threshold_for(threshold, scored_positions(b, q, ix->parts[f]));
     }
 }
 
@@ -287,6 +308,7 @@ cobs_gpu_status cobs_amd::run_impl(cobs_gpu_batch* b, double threshold, size_t t
     hipStream_t st = (hipStream_t)hip_stream;
     HIP_TRY(hipSetDevice(ix->device));
     set_run_state(b, threshold, topk, want_counts);
+    if (cobs_gpu_status fs = check_findere_lengths(b); fs != COBS_GPU_OK) return fs;
     const size_t nq = b->nq;
     const bool use_topk = b->topk_k != 0;
     // score rows are allocated by the first run that writes them (a hits-only caller never pays
@@ -781,9 +803,10 @@ cobs_gpu_status cobs_amd::run_impl(cobs_gpu_batch* b, double threshold, size_t t
                 sa.dbg_slots = ix->tune.phase_slots;
             }
             // measured variant (A/B only): rows staged through LDS, where that kernel exists
-            sa.lds_staged = ix->tune.lds_staged && !geom.multi_query && !p.idx64 &&
+            sa.lds_staged = ix->tune.lds_staged && !geom.multi_query && !p.idx64 && b->findere == 0 &&
                             scan_has_lds_staged(b->planes, (uint32_t)p.meta.num_hashes, nwaves) ? 1u : 0u;
             sa.exp = ix->tune.exp;
+            sa.findere = b->findere;
             sa.chunk_begin = 0;
             sa.chunk_end = c.total_chunks;
             // one launch covers at most 2^31-1 work-groups

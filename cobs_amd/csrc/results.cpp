@@ -115,13 +115,13 @@ static cobs_gpu_status rank_raw(const cobs_gpu_batch* b, size_t q, const uint8_t
     // pass 1: passing documents per score
     uint64_t max_score = 0;
     for (const Part& p : ix->parts)
-        max_score = std::max<uint64_t>(max_score, (uint64_t)b->lens[q] - p.meta.term_size + 1);
+        max_score = std::max<uint64_t>(max_score, scored_positions(b, q, p));
     if (max_score > (1u << 24)) return COBS_GPU_ERR_UNSUPPORTED;      // caller falls back to the generic sort
     hist.assign((size_t)max_score + 2, 0u);
     size_t passing = 0;
     for (size_t f = 0; f < ix->parts.size(); ++f) {
         const Part& p = ix->parts[f];
-        const uint32_t thr = threshold_for(b->threshold, (uint64_t)b->lens[q] - p.meta.term_size + 1);
+        const uint32_t thr = threshold_for(b->threshold, scored_positions(b, q, p));
         const uint64_t d0 = glob ? 0 : p.slot_begin;
         const uint64_t d1 = glob ? p.meta.doc_names.size()
                                  : std::min<uint64_t>(p.slot_begin + p.slot_count, p.meta.doc_names.size());
@@ -146,7 +146,7 @@ static cobs_gpu_status rank_raw(const cobs_gpu_batch* b, size_t q, const uint8_t
     // pass 2: scatter in (file, doc) order; positions >= want are dropped
     for (size_t f = 0; f < ix->parts.size(); ++f) {
         const Part& p = ix->parts[f];
-        const uint32_t thr = threshold_for(b->threshold, (uint64_t)b->lens[q] - p.meta.term_size + 1);
+        const uint32_t thr = threshold_for(b->threshold, scored_positions(b, q, p));
         const uint64_t d0 = glob ? 0 : p.slot_begin;
         const uint64_t d1 = glob ? p.meta.doc_names.size()
                                  : std::min<uint64_t>(p.slot_begin + p.slot_count, p.meta.doc_names.size());
@@ -477,7 +477,7 @@ static cobs_gpu_status hits_host_impl(cobs_gpu_batch* b, size_t q, size_t num_re
         if (st != COBS_GPU_OK) return st;
         for (size_t f = 0; f < ix->parts.size(); ++f) {
             const Part& p = ix->parts[f];
-            const uint32_t thr = threshold_for(b->threshold, (uint64_t)b->lens[q] - p.meta.term_size + 1);
+            const uint32_t thr = threshold_for(b->threshold, scored_positions(b, q, p));
             // only documents whose slots this shard computed
             const uint64_t d0 = b->view_global ? 0 : p.slot_begin;
             const uint64_t d1 = b->view_global ? p.meta.doc_names.size()

@@ -101,20 +101,29 @@ class Search:
     """cobs_index.Search: open one or several index files (classic or compact,
     auto-detected per file) and query them on the GPU."""
 
-    def __init__(self, path, device=-1, shard_rank=0, shard_count=1, hbm_budget=0, shard_mode=0, _handle=None):
+    def __init__(self, path, device=-1, shard_rank=0, shard_count=1, hbm_budget=0, shard_mode=0, _handle=None,
+                 findere=0):
         self._lib = _capi.load()
         self._h = C.c_void_p()
         if _handle is not None:
             self._h = _handle
+            if findere:
+                self.set_findere(findere)
             return
         paths = [path] if isinstance(path, (str, bytes, os.PathLike)) else list(path)
         arr = (C.c_char_p * len(paths))(*[os.fsencode(p) for p in paths])
         opts = _options(device, shard_rank, shard_count, hbm_budget, shard_mode)
         check(self._lib.cobs_gpu_open(arr, len(paths), C.byref(opts), C.byref(self._h)))
+        if findere:
+            try:
+                self.set_findere(findere)
+            except Exception:
+                self.close()
+                raise
 
     @classmethod
     def synthetic(cls, kind, signature_sizes, num_docs, page_size=0, term_size=31, canonicalize=1,
-                  num_hashes=1, seed=1, device=-1, shard_rank=0, shard_count=1, hbm_budget=0, shard_mode=0):
+                  num_hashes=1, seed=1, device=-1, shard_rank=0, shard_count=1, hbm_budget=0, shard_mode=0, findere=0):
         """Procedural index generated directly in HBM (benchmark / large parity runs)."""
         lib = _capi.load()
         sigs = (C.c_uint64 * len(signature_sizes))(*[int(s) for s in signature_sizes])
@@ -126,7 +135,14 @@ class Search:
         h = C.c_void_p()
         opts = _options(device, shard_rank, shard_count, hbm_budget, shard_mode)
         check(lib.cobs_gpu_open_synthetic(C.byref(d), C.byref(opts), C.byref(h)))
-        return cls(None, _handle=h)
+        s = cls(None, _handle=h)
+        if findere:
+            try:
+                s.set_findere(findere)
+            except Exception:
+                s.close()
+                raise
+        return s
 
     def close(self):
         if getattr(self, "_h", None):
@@ -186,6 +202,27 @@ class Search:
     def set_tuning(self, key, value):
         """per-handle tuning hook of the scan launch (see cobs_gpu_set_tuning)"""
         check(self._lib.cobs_gpu_set_tuning(self._h, key.encode(), int(value)))
+
+    @property
+    def findere(self):
+        """findere z (0..7): a position of a query scores in a document only when its z + 1 consecutive
+        k-mers are all present there; 0 = the plain COBS count (see cobs_gpu_set_findere)"""
+        z = C.c_uint32()
+        check(self._get_findere_call(C.byref(z)))
+        return z.value
+
+    def set_findere(self, z):
+        """set findere z (0..7) for every later search, count and batch run of this handle"""
+        z = int(z)
+        if not 0 <= z <= 7:
+            raise ValueError("findere: z is 0 .. 7")
+        check(self._set_findere_call(z))
+
+    def _set_findere_call(self, z):
+        return self._lib.cobs_gpu_set_findere(self._h, z)
+
+    def _get_findere_call(self, zp):
+        return self._lib.cobs_gpu_get_findere(self._h, zp)
 
     def read_rows(self, file_no, page, row0, nrows, out=None):
         """bulk D2H of whole rows of one held sub-index -> uint8 [nrows, held row bytes]"""
@@ -482,7 +519,7 @@ class MultiSearch(Search):
     device and the exchange over RCCL; search / search_batch / search_arrays / search_packed
     return exactly what Search returns on one GPU."""
 
-    def __init__(self, path, devices, hbm_budget=0, shard_mode=0):
+    def __init__(self, path, devices, hbm_budget=0, shard_mode=0, findere=0):
         self._lib = _capi.load()
         self._m = C.c_void_p()
         self._h = C.c_void_p()
@@ -493,6 +530,12 @@ class MultiSearch(Search):
         check(self._lib.cobs_gpu_multi_open(arr, len(paths), devs, len(devices), C.byref(opts), C.byref(self._m)))
         # rank 0's shard handle answers the geometry / name calls of the base class (not owned)
         self._h = C.c_void_p(self._lib.cobs_gpu_multi_index(self._m, 0))
+        if findere:
+            try:
+                self.set_findere(findere)
+            except Exception:
+                self.close()
+                raise
 
     def close(self):
         if getattr(self, "_m", None):
@@ -518,6 +561,12 @@ class MultiSearch(Search):
 
     def _search_batch_call(self, *args):
         return self._lib.cobs_gpu_multi_search_batch(self._m, *args)
+
+    def _set_findere_call(self, z):
+        return self._lib.cobs_gpu_multi_set_findere(self._m, z)
+
+    def _get_findere_call(self, zp):
+        return self._lib.cobs_gpu_multi_get_findere(self._m, zp)
 
     def counts(self, query):
         raise NotImplementedError("raw counts are per shard: use shard(rank).counts(query)")

@@ -2,7 +2,8 @@
  * include/cobs_gpu_batch.h -- the part of libcobs_gpu.so's C ABI that sits BESIDE the drop-in boundary
  * (include/cobs_gpu.h): device-resident query batches (inputs and counts stay in HBM: the benchmark's step, the
  * building blocks of the search calls), the one exchange step of the sub-index-sharded multi-GPU layout over RCCL
- * (one rank per process), cobs_gpu_search_batch over such a sharded index, and the procedural benchmark index.
+ * (one rank per process), cobs_gpu_search_batch over such a sharded index, the procedural benchmark index, and findere
+ * scoring (a query-time option beyond the reference's search).
  * Same conventions as cobs_gpu.h: plain pointers and sizes, cobs_gpu_status, nothing aborts.
  */
 #ifndef COBS_GPU_BATCH_H
@@ -33,6 +34,19 @@ typedef struct cobs_gpu_synth {
     uint64_t seed;
     const uint64_t* signature_sizes;   /* num_pages entries */
 } cobs_gpu_synth;
+
+/* ---- findere ------------------------------------------------------------ */
+/* findere (Robidou & Peterlongo, SPIRE 2021; kmindex -z), beyond the reference: with z in 1..7 a position p of
+ * the query scores in a document only when its z + 1 consecutive terms p .. p + z are all present there, which
+ * false-positive bits of the Bloom filters rarely are.  A query of T = |q| - k + 1 terms then has T - z positions:
+ * scores and max_counts count windows, thresholds are ceil(threshold * (T - z)), and a query needs k + z characters
+ * (COBS_GPU_ERR_QUERY_TOO_SHORT).  0 (the default) is the reference's count.  Every call and batch of the handle
+ * uses the z set when it runs.  ERR_ARG: NULL or z > 7; ERR_UNSUPPORTED: z > 0 on a handle with an HBM budget. */
+cobs_gpu_status cobs_gpu_set_findere(cobs_gpu_index* ix, uint32_t z);
+cobs_gpu_status cobs_gpu_get_findere(const cobs_gpu_index* ix, uint32_t* z);
+/* findere on every shard of the device list (the same rules as cobs_gpu_set_findere; no shard changes on error) */
+cobs_gpu_status cobs_gpu_multi_set_findere(cobs_gpu_multi* m, uint32_t z);
+cobs_gpu_status cobs_gpu_multi_get_findere(const cobs_gpu_multi* m, uint32_t* z);
 
 /* ---- procedural index ---------------------------------------------------- */
 cobs_gpu_status cobs_gpu_open_synthetic(const cobs_gpu_synth* desc,

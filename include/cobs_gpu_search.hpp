@@ -269,6 +269,15 @@ public:
 
     cobs_gpu_index* handle() const override { return ix_; }
 
+    //! findere z (0..7, beyond the reference): a position scores only when its z + 1 consecutive terms are all present
+    //! (cobs_gpu_set_findere); 0 = the reference's count
+    void set_findere(unsigned z) { check(cobs_gpu_set_findere(ix_, z)); }
+    unsigned findere() const {
+        uint32_t z = 0;
+        check(cobs_gpu_get_findere(ix_, &z));
+        return z;
+    }
+
 private:
     static void check(cobs_gpu_status st) {
         if (st != COBS_GPU_OK) throw Error(st, cobs_gpu_last_error());
@@ -354,6 +363,13 @@ public:
     }
     //! ncclCommCount of the communicator the GPUs joined
     int comm_size() const { return (int)cobs_gpu_multi_size(m_); }
+    //! findere z on every shard (see ClassicSearch::set_findere)
+    void set_findere(unsigned z) { check(cobs_gpu_multi_set_findere(m_, z)); }
+    unsigned findere() const {
+        uint32_t z = 0;
+        check(cobs_gpu_multi_get_findere(m_, &z));
+        return z;
+    }
 
 private:
     static void check(cobs_gpu_status st) {
