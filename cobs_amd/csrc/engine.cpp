@@ -605,8 +605,11 @@ cobs_gpu_status cobs_gpu_set_tuning(cobs_gpu_index* ix, const char* key, int64_t
         t.row_fetch_alpha = value >= 0 ? (uint32_t)std::min<int64_t>(value, 1 << 20) : 1;   // 0: whenever the rows fit
     } else if (k == "phase_slots") {
         t.phase_slots = value > 0 ? (uint32_t)std::min<int64_t>(value, 1 << 20) : 0;
+    } else if (k == "hit_cap") {
+        if (value < 0) return fail(COBS_GPU_ERR_ARG, "hit_cap: 0 (the pool's capacity) or a positive record count");
+        t.hit_cap = (uint64_t)value;
     } else {
-        return fail(COBS_GPU_ERR_ARG, "unknown tuning key (waves, tile_w, mq, pass_bytes, pipe_chars, graph, lds_staged, device_rank, rank_pack, rank_slim, rank_segments, rank_window_kib, hash_stream, tile_topk, row_fetch, row_fetch_alpha, min_score_bytes)");
+        return fail(COBS_GPU_ERR_ARG, "unknown tuning key (waves, tile_w, mq, pass_bytes, pipe_chars, graph, lds_staged, device_rank, rank_pack, rank_slim, rank_segments, rank_window_kib, hash_stream, tile_topk, row_fetch, row_fetch_alpha, min_score_bytes, hit_cap)");
     }
     return COBS_GPU_OK;
 }
@@ -824,6 +827,31 @@ cobs_gpu_status cobs_gpu_stream_plan(const cobs_gpu_index* ix, uint64_t out[4]) 
     out[1] = ix->stream.resident_bytes;
     out[2] = ix->stream.pass_bytes;
     out[3] = chunks;
+    return COBS_GPU_OK;
+}
+
+cobs_gpu_status cobs_gpu_stream_layout(const cobs_gpu_index* ix, size_t file_no, uint64_t out[4]) {
+    if (!ix || !out) return fail(COBS_GPU_ERR_ARG, "NULL argument");
+    if (file_no >= ix->parts.size()) return fail(COBS_GPU_ERR_ARG, "file number out of range");
+    const Part& p = ix->parts[file_no];
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (!p.streamed) {
+        out[0] = p.held.size();
+        return COBS_GPU_OK;
+    }
+    for (const Chunk& c : p.chunks) {
+        if (c.resident) {
+            out[0] += c.vp.size();
+        } else if (c.row_range) {
+            out[3] += 1;
+        } else {
+            // a column slice: the chunk's one slice is narrower than what this shard holds of its sub-index
+            bool sliced = false;
+            for (const VPage& h : p.held)
+                if (c.vp.size() == 1 && h.fp == c.vp[0].fp && h.ncols > c.vp[0].ncols) sliced = true;
+            out[sliced ? 2 : 1] += 1;
+        }
+    }
     return COBS_GPU_OK;
 }
 

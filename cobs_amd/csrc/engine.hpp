@@ -120,6 +120,8 @@ struct Tuning {
     uint32_t exp = 0;           // experimental kernel variants under A/B measurement (bit field, ScanArgs::exp)
     bool trace = false;         // COBS_GPU_TRACE: where the host side of a search call spends its time, on stderr
     uint32_t phase_slots = 0;   // tuning builds (make timing): work-groups of a scan launch that record phase stamps
+    uint64_t hit_cap = 0;       // tests: at most this many records in a batch's hit pool (0 = its full capacity); lowers the
+                                // cap the kernels honour, never the allocation -- small fixtures reach the overflow paths
     static Tuning from_env();
 };
 
@@ -176,7 +178,8 @@ struct Part {
     CountPage* d_cpages = nullptr;
     uint32_t ncounters = 0;
     bool streamed = false;
-    bool has_row_ranges = false;             // some chunk is a row range: K2 cannot select on its partial counts (pass.cpp)
+    bool has_row_ranges = false;             // some chunk is a row range: K2 does not select on its partial counts, the
+                                             // selection runs over the added-up scores after the last range (pass.cpp)
     bool idx64 = false;                      // a sub-index has >= 2^32 - 1 rows: 64-bit row-index table
     size_t hbm_bytes = 0;
     uint64_t resident_bytes = 0;             // what the held slices need when they stay in HBM

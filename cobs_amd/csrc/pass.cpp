@@ -203,7 +203,8 @@ cobs_gpu_status cobs_amd::set_queries_on(cobs_gpu_batch* b, const char* const* q
     // selection pool: room for 1024 hits per query, at least 1 Mi entries
     const uint64_t want = std::min<uint64_t>(std::max<uint64_t>(1u << 20, nq * 1024ull), 1ull << 26);
     HIP_TRY(b->hits.reserve((size_t)want));
-    b->hit_cap = (uint32_t)b->hits.cap;
+    // (tuning key hit_cap lowers the cap the kernels honour, never raises it past the allocation)
+    b->hit_cap = (uint32_t)(ix->tune.hit_cap ? std::min<uint64_t>(b->hits.cap, ix->tune.hit_cap) : b->hits.cap);
     HIP_TRY(b->h_thr_stage.reserve(std::max<size_t>(nq * ix->parts.size(), 1)));
     b->stats[0] = algo_bytes + (uint64_t)nq * ix->local_counts * b->elem_bytes;      // until a run says otherwise
     b->stats[1] = 0;
@@ -237,6 +238,7 @@ uint64_t cobs_amd::pass_shape_class(const cobs_gpu_batch* b) {
     for (size_t q = 0; q < nq && !single; ++q) single = total_hashes(b, q) <= 1;
     mixin(single);
     mixin(b->findere);             // a kernel argument of the captured scan (and its instantiation)
+    mixin(b->hit_cap);             // ... and so is the pool's cap
     for (size_t f = 0; f < ix->parts.size() && nq; ++f) {
         const Part& p = ix->parts[f];
         for (const Chunk& c : p.chunks) {
@@ -280,10 +282,10 @@ void cobs_amd::set_run_state(cobs_gpu_batch* b, double threshold, size_t topk, b
         for (size_t q = 0; ok && q < b->nq; ++q) ok = total_hashes(b, q) > 1;
         b->topk_direct = ok;
     }
-    // (A streamed sub-index cut into ROW ranges is counted range by range: K2 sees partial counts there.  Its ranges add
-    // up in a scratch matrix of the sub-index's own width and the selection runs over that after the last range --
-    // run_impl, `acc_mode` --, so such a handle selects like any other.  Until round 6 it kept score rows of the whole
-    // index instead and answered hits and limits from them.)
+    // (A streamed sub-index cut into ROW ranges is counted range by range: K2 sees partial counts there and never
+    // selects on them.  A pass without score rows adds its ranges up in a scratch matrix of the sub-index's own width,
+    // one that keeps them adds them up in the rows; either way the selection runs over the complete scores after the
+    // sub-index's last range (run_impl: `acc_mode`, `rows_select`), so such a handle selects like any other.)
     b->have_counts = want_counts || (!b->selected && !b->topk_direct);
 }
 
@@ -562,6 +564,9 @@ cobs_gpu_status cobs_amd::run_impl(cobs_gpu_batch* b, double threshold, size_t t
             // resident path fills (reference: the filter is the same whatever back-end gathered the rows,
             // classic_search.cpp:127-145).  C3's largest sub-index, 10k queries: 250 MB of scratch instead of 2 GB of rows.
             const bool acc_mode = c.row_range && !b->have_counts && (b->selected || b->topk_direct);
+            // ... and a thresholded pass that KEEPS the score rows: the ranges add up there, and the same selection runs
+            // over the sub-index's slots of the rows after its last range (K2 of a range never sees a complete score)
+            const bool rows_select = c.row_range && b->have_counts && b->selected;
             const PageDev* pages_dev = (partial || acc_mode) ? c.d_pages_acc : c.d_pages;
             const void* table_dev = b->work[f].table.p;
             bool unit_fetched = false;
@@ -767,7 +772,7 @@ cobs_gpu_status cobs_amd::run_impl(cobs_gpu_batch* b, double threshold, size_t t
             sa.table = table_dev;
             sa.blk_off = blk_dev;
             sa.counts = partial ? b->counts_part.p : acc_mode ? b->counts_acc.p : b->counts.p;
-            sa.thresholds = (b->selected && !acc_mode) ? b->work[f].thr.p : nullptr;
+            sa.thresholds = (b->selected && !c.row_range) ? b->work[f].thr.p : nullptr;
             sa.hits = b->hits.p;
             sa.hit_count = reinterpret_cast<unsigned long long*>(b->flags.p + 2);
             sa.counts_stride = (partial || acc_mode) ? part_slots : ix->local_counts;
@@ -833,17 +838,21 @@ cobs_gpu_status cobs_amd::run_impl(cobs_gpu_batch* b, double threshold, size_t t
                 HIP_TRY(launch_add_scores(aa, st));
             }
             // the last range of the sub-index in this pass (its ranges are consecutive units): select from what they added up
-            const bool last_range = acc_mode && (ci + 1 == units[f].size() || !units[f][ci + 1]->row_range ||
-                                                 units[f][ci + 1]->vp[0].fp != c.vp[0].fp);
+            const bool last_range = (acc_mode || rows_select) && (ci + 1 == units[f].size() || !units[f][ci + 1]->row_range ||
+                                                                  units[f][ci + 1]->vp[0].fp != c.vp[0].fp);
             if (last_range) {
-                const uint32_t nvalid = std::min<uint32_t>(part_slots, c.pages[0].valid_bytes * 8u);
+                const uint32_t sub_slots = (uint32_t)(c.vp[0].ncols * 8);
+                const uint32_t nvalid = std::min<uint32_t>(sub_slots, c.pages[0].valid_bytes * 8u);
                 if (b->selected) {
+                    // (the sub-index's slots of the rows start at local_offset + slot0, a multiple of 8 as local_counts is:
+                    // the 8-score groups select_rows_kernel loads stay aligned)
                     SelectRowsArgs sr;
-                    sr.scores = b->counts_acc.p;
+                    sr.scores = acc_mode ? (const void*)b->counts_acc.p
+                                         : (const void*)(b->counts.p + (p.local_offset + c.pages[0].slot0) * b->elem_bytes);
                     sr.thresholds = b->work[f].thr.p;
                     sr.hits = b->hits.p;
                     sr.hit_count = reinterpret_cast<unsigned long long*>(b->flags.p + 2);
-                    sr.stride = part_slots;
+                    sr.stride = acc_mode ? part_slots : ix->local_counts;
                     sr.nslots = nvalid;
                     sr.nq = (uint32_t)nq;
                     sr.elem_bytes = b->elem_bytes;
@@ -876,7 +885,7 @@ cobs_gpu_status cobs_amd::run_impl(cobs_gpu_batch* b, double threshold, size_t t
                     ta.sort_limit = (uint32_t)topk;
                     HIP_TRY(launch_topk(ta, st));
                 }
-                tile_base += 1;
+                if (acc_mode) tile_base += 1;    // (rows_select: no candidate pool, topk_direct is off)
             }
             if (stream_this) {
                 HIP_TRY(hipEventRecord(sbufs.scanned[buf], st));

@@ -507,6 +507,13 @@ class Search:
         check(self._lib.cobs_gpu_stream_plan(self._h, C.byref(c)))
         return int(c[0]), int(c[1]), int(c[2]), int(c[3])
 
+    def stream_layout(self, file_no=0):
+        """how file `file_no` is held: (slices resident in HBM, streamed chunks of whole slices, streamed column slices,
+        streamed row ranges)"""
+        c = (C.c_uint64 * 4)()
+        check(self._lib.cobs_gpu_stream_layout(self._h, int(file_no), C.byref(c)))
+        return int(c[0]), int(c[1]), int(c[2]), int(c[3])
+
     def timers(self, reset=False):
         t = (C.c_double * 5)()
         check(self._lib.cobs_gpu_timers(self._h, C.byref(t), 1 if reset else 0))

@@ -128,7 +128,9 @@ void cobs_gpu_close(cobs_gpu_index* ix);
  * "row_fetch_alpha", "min_score_bytes" (2 / 4: score rows at least that wide -- the reference's
  * classic_search_disable_8bit / _16bit switches, classic_search.cpp:207-209); "rank_pack" / "rank_slim" / "rank_window_kib" / "rank_segments"
  * (how the ranked results of the default call cross PCIe: 4-byte records, slot streams, piece size; work-groups per row), "compact_terms",
- * "hash_stream": A/B switches named where DESIGN.md 3 describes what they switch.  0 / -1 = automatic. */
+ * "hash_stream": A/B switches named where DESIGN.md 3 describes what they switch.  0 / -1 = automatic.
+ * "hit_cap" (tests): a batch's hit pool keeps at most that many records (0 = its full capacity, at least 1 Mi) -- it
+ * lowers the cap only, so that small indexes reach the overflow paths; set before the queries of the batch. */
 cobs_gpu_status cobs_gpu_set_tuning(cobs_gpu_index* ix, const char* key, int64_t value);
 size_t cobs_gpu_num_files(const cobs_gpu_index* ix);
 cobs_gpu_status cobs_gpu_info(const cobs_gpu_index* ix, size_t file_no, cobs_gpu_index_info* info);

@@ -108,6 +108,10 @@ cobs_gpu_status cobs_gpu_stream_traffic(const cobs_gpu_index* ix, uint64_t out[4
  * copies every other chunk whole, out[3] = number of those chunks.  COBS_GPU_STREAM_BUF_KIB (read when the index is
  * opened) bounds a stream buffer (default 256 MiB, 0 = half the budget as in rounds 1-4). */
 cobs_gpu_status cobs_gpu_stream_plan(const cobs_gpu_index* ix, uint64_t out[4]);
+/* How file `file_no` of the handle is laid out (what the plan decided when the index was opened): out[0] = held slices
+ * that stay in HBM (every one of a resident file), out[1] = streamed chunks of whole slices (one or several sub-indexes
+ * each), out[2] = streamed column slices of a sub-index, out[3] = streamed row ranges of a sub-index. */
+cobs_gpu_status cobs_gpu_stream_layout(const cobs_gpu_index* ix, size_t file_no, uint64_t out[4]);
 /* The same plan as host arithmetic, without a device (what cobs_gpu_open would decide for `path` under the budget and
  * the shard options): out as above (for a file that fits: out[1] = its bytes, the rest 0); resident[i] (optional, `cap`
  * entries; *n_slices = how many there are) = 1 if the i-th held slice stays in HBM.  For tests of the planner. */

@@ -279,6 +279,14 @@ def test_row_range_chunks(gpu_lib, oracle, tmp_path, monkeypatch, kind, no_pin):
     assert b.stats()["scan_launches"] >= 4
     for i, q in enumerate(queries):
         assert np.array_equal(b.counts_host(i), ix.counts(q))
+    # a thresholded pass that keeps the score rows: the hit pool is filled from the added-up scores of the ranges, not
+    # from any range's partial counts
+    for t in (0.05, 0.4, 0.9):
+        b.run(t)
+        b.sync()
+        for i, q in enumerate(queries):
+            assert b.hits_host(i) == cases.oracle_results([ix], q, t, 0), (t, i)
+            assert np.array_equal(b.counts_host(i), ix.counts(q)), (t, i)
     for t, lim in ((0.0, 0), (0.4, 0), (0.4, 3), (0.9, 0)):
         assert s.search_hits(queries, t, lim) == [cases.oracle_results([ix], q, t, lim) for q in queries], (t, lim)
     # short queries only: 8-bit scores through the same accumulation
