@@ -29,7 +29,10 @@
 static void usage() {
     std::fprintf(stderr,
                  "usage: cobs_gpu_query -i INDEX [-i INDEX ...] [-t THRESHOLD] [-l LIMIT] "
-                 "[-d DEVICE[,DEVICE...]] [--hbm-budget GIB] [--findere Z] (QUERY | -f QUERY_FILE)\n"
+                 "[-d DEVICE[,DEVICE...]] [--hbm-budget GIB] [--findere Z] [--positions] (QUERY | -f QUERY_FILE)\n"
+                 "       --positions: every result line gets a tab and one character per position of the query in that\n"
+                 "        document, position 0 first: 1 = the k-mer there (with --findere Z: all Z + 1 from there) is present;\n"
+                 "        the number of 1s is the score.  Not with several devices or --hbm-budget.\n"
                  "       --findere Z (0..7): a k-mer position scores only when Z + 1 consecutive k-mers are all present\n"
                  "        (findere, beyond `cobs query`: far fewer false-positive k-mers; a query needs k + Z characters)\n"
                  "       -d 0,1,2,3: the index is sharded by sub-index block over the listed GPUs, every search is\n"
@@ -150,6 +153,29 @@ static int benchmark(cobs_gpu::BatchSearch& s, const std::string& index, unsigne
 // and rows (/ add rows); here: hashes (K1), h2d (query text), scan (K2: gather + AND + count), d2h, rank.
 static void print_timer(const cobs_gpu::BatchSearch& s) { s.timer().print("search"); }
 
+// --positions: the words of one result as n characters 0 / 1, position 0 first
+static std::string position_string(const std::vector<uint64_t>& words, size_t n) {
+    std::string out(n, '0');
+    for (size_t p = 0; p < n && p / 64 < words.size(); ++p)
+        if ((words[p / 64] >> (p % 64)) & 1u) out[p] = '1';
+    return out;
+}
+
+// the queries of a `query` call with --positions: the result lines of `cobs query`, each with its 0/1 string appended
+static void print_with_positions(cobs_gpu::ClassicSearch& s, const std::vector<std::string>& queries,
+                                 const std::vector<std::string>* comments, double threshold, size_t num_results) {
+    std::vector<std::vector<cobs_gpu::SearchResult>> results;
+    std::vector<std::vector<std::vector<uint64_t>>> pos;
+    std::vector<std::vector<size_t>> npos;
+    s.search_batch_positions(queries, results, pos, threshold, num_results, &npos);
+    for (size_t q = 0; q < queries.size(); ++q) {
+        if (comments) std::cout << (*comments)[q] << '\t' << results[q].size() << '\n';
+        for (size_t i = 0; i < results[q].size(); ++i)
+            std::cout << results[q][i].doc_name << '\t' << results[q][i].score << '\t'
+                      << position_string(pos[q][i], npos[q][i]) << '\n';
+    }
+}
+
 int cobs_gpu_tools_main(int argc, char** argv);      // cobs_gpu_tools.cpp: *-construct, classic-combine, compact-construct-combine
 
 int main(int argc, char** argv) {
@@ -174,6 +200,7 @@ int main(int argc, char** argv) {
     uint64_t synth_docs = 10000, synth_page = 0, synth_hashes = 1;
     bool bench = fpr_mode, dist = false;
     int findere = -1;                        // --findere Z; -1: not given (the handle's default, 0)
+    bool positions = false;                  // --positions
     unsigned num_kmers = 1000, num_queries = 10000, num_warmup = 100;
     size_t seed = std::random_device{}();
     for (int i = 1; i < argc; ++i) {
@@ -221,12 +248,18 @@ int main(int argc, char** argv) {
             if (v.empty() || *end != '\0' || z < 0 || z > 7) { std::fprintf(stderr, "--findere: 0 .. 7\n"); return 1; }
             findere = (int)z;
         }
+        else if (a == "--positions") positions = true;
         else if (a == "-h" || a == "--help") { usage(); return 0; }
         else if (!a.empty() && a[0] == '-') { std::fprintf(stderr, "unknown flag %s\n", a.c_str()); usage(); return 1; }
         else if (fpr_mode && index_paths.empty()) index_paths.push_back(a);
         else query_line = a;
     }
     const int device = devices.empty() ? -1 : devices[0];
+    if (positions && (devices.size() > 1 || force_sharded || hbm_budget != 0)) {
+        std::fprintf(stderr, "--positions: not with several devices (-d A,B / --sharded) or --hbm-budget: "
+                             "the rows of a document have to be resident on one GPU\n");
+        return 1;
+    }
     auto open_index = [&]() -> std::unique_ptr<cobs_gpu::BatchSearch> {
         // stdout carries the results in `cobs query` format and nothing else: RCCL prints a
         // version banner there when a communicator is created, so stdout points at stderr
@@ -299,6 +332,12 @@ int main(int argc, char** argv) {
     try {
         std::unique_ptr<cobs_gpu::BatchSearch> sp = open_index();
         cobs_gpu::BatchSearch& s = *sp;
+        if (!query_line.empty() && positions) {
+            print_with_positions(dynamic_cast<cobs_gpu::ClassicSearch&>(s), {query_line}, nullptr, threshold, num_results);
+            std::cout.flush();
+            print_timer(s);
+            return 0;
+        }
         if (!query_line.empty()) {
             std::vector<cobs_gpu::SearchResult> result;
             s.search(query_line, result, threshold, num_results);
@@ -323,6 +362,12 @@ int main(int argc, char** argv) {
             }
         }
         if (!query.empty()) { queries.push_back(query); comments.push_back(comment); }
+        if (positions) {
+            print_with_positions(dynamic_cast<cobs_gpu::ClassicSearch&>(s), queries, &comments, threshold, num_results);
+            std::cout.flush();
+            print_timer(s);
+            return 0;
+        }
         std::vector<std::vector<cobs_gpu::SearchResult>> results;
         s.search_batch(queries, results, threshold, num_results);
         for (size_t q = 0; q < queries.size(); ++q) {

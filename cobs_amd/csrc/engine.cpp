@@ -155,6 +155,7 @@ cobs_gpu_batch::~cobs_gpu_batch() {
 }
 
 cobs_gpu_index::~cobs_gpu_index() {
+    if (positions) destroy_positions_work(positions);
     for (auto* b : scratch) delete b;
     if (xchg_stream) (void)hipStreamDestroy(xchg_stream);
 }

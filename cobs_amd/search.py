@@ -82,6 +82,12 @@ def _split_segments(hits, offs, nq, threshold, num_results, search):
     return [rows[int(offs[q]):int(offs[q + 1])] for q in range(nq)]
 
 
+def unpack_positions(words, n):
+    """the words of one hit (Search.hit_positions) -> bool [n]: position p is bit p % 64 of word p // 64"""
+    w = np.ascontiguousarray(words, dtype="<u8")
+    return np.unpackbits(w.view(np.uint8), bitorder="little")[:n].astype(bool)
+
+
 def _as_bytes(q):
     return q.encode("latin-1") if isinstance(q, str) else bytes(q)
 
@@ -478,6 +484,67 @@ class Search:
         check(self._lib.cobs_gpu_counts(self._h, q, len(q), out.ctypes.data, out.size))
         return out
 
+    # -- positions: WHERE in each query its hits matched --------------------------
+    def hit_positions(self, queries, offsets, hits):
+        """cobs_gpu_hit_positions over a hit list as search_arrays returned it (hits[offsets[i]:offsets[i + 1]] belong to
+        query i; the scores are ignored, so any (file_no, doc) pairs may be asked about)
+        -> (bit_offsets uint64 [n_hits + 1], bits uint64): hit i owns the words bits[bit_offsets[i]:bit_offsets[i + 1]];
+        position p of its query is bit p % 64 of word p // 64 and is set when the terms p .. p + findere are all present
+        in the document -- the popcount of a hit's words is its score (unpack_positions gives the bool vector)."""
+        if type(self)._search_batch_call is not Search._search_batch_call:
+            raise CobsGpuError(_capi.ERR_UNSUPPORTED, "positions: not on a device-list handle (a document's rows live on one rank)")
+        qs = [q if type(q) is bytes else _as_bytes(q) for q in queries]
+        nq = len(qs)
+        offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if len(offs) != nq + 1:
+            raise ValueError("offsets needs nq + 1 entries")
+        n = int(offs[nq])
+        hits = np.ascontiguousarray(hits, dtype=self.HIT_DTYPE)
+        if len(hits) < n:
+            raise ValueError("hits is shorter than offsets[nq]")
+        arr = (C.c_char_p * max(nq, 1))(*qs)
+        lens = (C.c_size_t * max(nq, 1))(*[len(q) for q in qs])
+        bit_offsets = np.zeros(n + 1, dtype=np.uint64)
+        need, bad = C.c_size_t(0), C.c_size_t(0)
+        # the number of words is host arithmetic (the call refuses a buffer that is too small before any device work):
+        # ask for it, then make the call
+        bits = np.zeros(0, dtype=np.uint64)
+        while True:
+            st = self._lib.cobs_gpu_hit_positions(
+                self._h, arr, lens, nq, C.cast(hits.ctypes.data, C.POINTER(Hit)),
+                C.cast(offs.ctypes.data, C.POINTER(C.c_size_t)), C.cast(bits.ctypes.data, C.POINTER(C.c_uint64)), bits.size,
+                C.cast(bit_offsets.ctypes.data, C.POINTER(C.c_size_t)), C.byref(need), C.byref(bad))
+            if st == _capi.ERR_CAPACITY and need.value > bits.size:
+                bits = np.zeros(need.value, dtype=np.uint64)
+                continue
+            check(st)
+            break
+        return bit_offsets, bits
+
+    def search_positions(self, queries, threshold=0.0, num_results=0):
+        """search_arrays followed by hit_positions -> (offsets, hits, bit_offsets, bits)"""
+        qs = [q if type(q) is bytes else _as_bytes(q) for q in queries]
+        offsets, hits = self.search_arrays(qs, threshold, num_results)
+        bit_offsets, bits = self.hit_positions(qs, offsets, hits)
+        return offsets, hits, bit_offsets, bits
+
+    def search_with_positions(self, query, threshold=0.0, num_results=0):
+        """one query -> [(SearchResult, bool ndarray of its n positions)] in result order"""
+        q = _as_bytes(query)
+        offsets, hits, bit_offsets, bits = self.search_positions([q], threshold, num_results)
+        out = []
+        for i, (f, d, sc) in enumerate(hits.tolist()):
+            n = len(q) - int(self.info(f).term_size) + 1 - self.findere
+            out.append((SearchResult(self.doc_name(f, d), sc),
+                        unpack_positions(bits[int(bit_offsets[i]):int(bit_offsets[i + 1])], n)))
+        return out
+
+    def positions_ms(self):
+        """kernel times of the hit_positions calls since the previous call of this method (HIP events, summed over passes)"""
+        t = (C.c_double * 3)()
+        check(self._lib.cobs_gpu_positions_ms(self._h, C.byref(t)))
+        return {"presence_ms": t[0], "hash_ms": t[1], "passes": int(t[2])}
+
     @property
     def graph_replays(self):
         """small host-API passes served by a captured hipGraph so far"""
@@ -739,7 +806,7 @@ class Batch:
         return {"scan_ms": a.value, "hash_ms": b.value}
 
 
-__all__ = ["Search", "SearchResult", "Batch", "CobsGpuError"]
+__all__ = ["Search", "SearchResult", "Batch", "CobsGpuError", "unpack_positions"]
 
 
 class ShardedBatch:

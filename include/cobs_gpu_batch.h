@@ -81,6 +81,25 @@ cobs_gpu_status cobs_gpu_search_batch_view(cobs_gpu_index* ix, const char* const
                                            double threshold, size_t num_results, const cobs_gpu_hit** hits,
                                            const size_t** hit_offsets, size_t* bad_query);
 
+/* WHERE in each query its hits matched: for the hit list a search call returned (hits[hit_offsets[j] .. hit_offsets[j+1])
+ * belong to query j; `score` of the records is ignored, so any (file, document) pairs may be asked about) the per-position
+ * presence vector of every hit.  With T = len - term_size(file) + 1 terms and the handle's findere z, a hit has
+ * n = T - z positions; position p is set when terms p .. p + z are all present in the document (every term: all of the
+ * file's hash bits set in the document's column, as the scan counts it).  Hit i owns the words
+ * bits[bit_offsets[i] .. bit_offsets[i+1]) (bit_offsets: n_hits + 1 entries, in 64-bit words; ceil(n / 64) words per hit),
+ * position p is bit p % 64 of word p / 64, bits >= n of the last word are 0 -- the popcount of a hit's words is the score
+ * the search reported for it.  A second call over a hit list, not part of the scan: it hashes the queries that have hits
+ * again and reads one bit per looked-up row.
+ * Errors as cobs_gpu_search_batch reports them (*bad_query = the offending query); COBS_GPU_ERR_ARG for a file or
+ * document number out of range or descending offsets; COBS_GPU_ERR_CAPACITY when cap_words is too small -- bit_offsets
+ * and *words_needed (optional) are filled, so the call can be repeated (bits may be NULL when cap_words is 0);
+ * COBS_GPU_ERR_UNSUPPORTED on a handle opened with an HBM budget or as one shard of several (the rows are not all
+ * resident there). */
+cobs_gpu_status cobs_gpu_hit_positions(cobs_gpu_index* ix, const char* const* queries, const size_t* lens,
+                                       size_t nq, const cobs_gpu_hit* hits, const size_t* hit_offsets,
+                                       uint64_t* bits, size_t cap_words, size_t* bit_offsets,
+                                       size_t* words_needed, size_t* bad_query);
+
 /* score slots per query held by THIS shard (== cobs_gpu_total_counts when
  * unsharded); device count rows have this many elements */
 uint64_t cobs_gpu_local_counts(const cobs_gpu_index* ix);

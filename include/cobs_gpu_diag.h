@@ -75,6 +75,10 @@ cobs_gpu_status cobs_gpu_batch_stats(const cobs_gpu_batch* b, uint64_t out[4]);
  * stream the kernels were launched on.  Call after cobs_gpu_batch_sync. */
 cobs_gpu_status cobs_gpu_batch_kernel_ms(cobs_gpu_batch* b, float* scan_ms, float* hash_ms);
 
+/* HIP-event durations (ms) of the kernels of the cobs_gpu_hit_positions calls on this handle since the previous call of
+ * this function, summed over their passes: out[0] = the presence kernel, out[1] = K1 (hashing), out[2] = passes. */
+cobs_gpu_status cobs_gpu_positions_ms(cobs_gpu_index* ix, double out[3]);
+
 /* Diagnostics of tuning builds (libcobs_gpu_timing.so, `make -C cobs_amd/csrc timing`): s_memtime stamps
  * [work-group slot][wave 0..3][8 phases] of the work-groups sampled from the last scan launch after
  * cobs_gpu_set_tuning(ix, "phase_slots", n).  The production library records nothing (*n_words = 0). */

@@ -269,6 +269,61 @@ public:
 
     cobs_gpu_index* handle() const override { return ix_; }
 
+    //! search() plus WHERE in the query each result matched (beyond the reference; cobs_gpu_hit_positions):
+    //! positions[i] holds the words of result[i] -- position p of the query's n = T - z positions is bit p % 64 of word
+    //! p / 64, set when the terms p .. p + z are all present in the document; their popcount is result[i].score
+    void search_positions(const std::string& query, std::vector<SearchResult>& result,
+                          std::vector<std::vector<uint64_t>>& positions, double threshold = 0.0, size_t num_results = 0) {
+        std::vector<std::vector<SearchResult>> rs;
+        std::vector<std::vector<std::vector<uint64_t>>> ps;
+        search_batch_positions({query}, rs, ps, threshold, num_results);
+        result = std::move(rs[0]);
+        positions = std::move(ps[0]);
+    }
+
+    //! ... for many queries: positions[q] is parallel to results[q]; num_positions (optional) receives every result's
+    //! n = T - z, which depends on the term size of the index file that holds the document
+    void search_batch_positions(const std::vector<std::string>& queries, std::vector<std::vector<SearchResult>>& results,
+                                std::vector<std::vector<std::vector<uint64_t>>>& positions, double threshold = 0.0,
+                                size_t num_results = 0, std::vector<std::vector<size_t>>* num_positions = nullptr) {
+        std::vector<const char*> qp;
+        std::vector<size_t> ql;
+        for (const auto& q : queries) { qp.push_back(q.data()); ql.push_back(q.size()); }
+        const size_t nq = queries.size();
+        const cobs_gpu_hit* vh = nullptr;
+        const size_t* vo = nullptr;
+        size_t bad = 0, need = 0;
+        // (the hits stay in the library's arena, which the positions call reads them from: it is not a search call)
+        check(cobs_gpu_search_batch_view(ix_, qp.data(), ql.data(), nq, threshold, num_results, &vh, &vo, &bad));
+        std::vector<size_t> bo(vo[nq] + 1, 0);
+        std::vector<uint64_t> bits;
+        cobs_gpu_status st = cobs_gpu_hit_positions(ix_, qp.data(), ql.data(), nq, vh, vo, nullptr, 0, bo.data(), &need, &bad);
+        if (st == COBS_GPU_ERR_CAPACITY && need > 0) {       // the size is host arithmetic: nothing has run yet
+            bits.resize(need);
+            st = cobs_gpu_hit_positions(ix_, qp.data(), ql.data(), nq, vh, vo, bits.data(), bits.size(), bo.data(), &need, &bad);
+        }
+        check(st);
+        std::vector<size_t> term_size(cobs_gpu_num_files(ix_));
+        for (size_t f = 0; f < term_size.size(); ++f) {
+            cobs_gpu_index_info info;
+            check(cobs_gpu_info(ix_, f, &info));
+            term_size[f] = info.term_size;
+        }
+        const size_t z = findere();
+        results.resize(nq);
+        positions.resize(nq);
+        if (num_positions) num_positions->assign(nq, {});
+        for (size_t q = 0; q < nq; ++q) {
+            results[q].resize(vo[q + 1] - vo[q]);
+            positions[q].resize(vo[q + 1] - vo[q]);
+            for (size_t i = vo[q]; i < vo[q + 1]; ++i) {
+                if (num_positions) (*num_positions)[q].push_back(ql[q] - term_size[vh[i].file_no] + 1 - z);
+                results[q][i - vo[q]] = SearchResult(cobs_gpu_doc_name(ix_, vh[i].file_no, vh[i].doc), vh[i].score);
+                positions[q][i - vo[q]].assign(bits.begin() + bo[i], bits.begin() + bo[i + 1]);
+            }
+        }
+    }
+
     //! findere z (0..7, beyond the reference): a position scores only when its z + 1 consecutive terms are all present
     //! (cobs_gpu_set_findere); 0 = the reference's count
     void set_findere(unsigned z) { check(cobs_gpu_set_findere(ix_, z)); }
