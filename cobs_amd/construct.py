@@ -147,6 +147,7 @@ class ClassicIndexParameters:
         self.clobber = False
         self.continue_ = False
         self.keep_temporary = False
+        self.min_count = 1          # k-mer abundance cutoff per document, 0 / 1 = off (not in the reference)
 
 
 class CompactIndexParameters(ClassicIndexParameters):
@@ -167,6 +168,7 @@ def _params(p, device):
     b.device = device
     b.text_batch_bytes = int(getattr(p, "text_batch_bytes", 0))
     b.set_bits_mode = int(getattr(p, "set_bits_mode", 0))
+    b.min_count = int(getattr(p, "min_count", 1))
     return b
 
 

@@ -24,6 +24,7 @@
 #include <tuple>
 #include <vector>
 
+#include "abundance_kernels.hpp"
 #include "documents.hpp"
 #include "engine.hpp"
 #include "staging.hpp"
@@ -65,6 +66,7 @@ struct Params {
     const uint64_t* doc_terms = nullptr;
     uint64_t text_batch = 0;
     uint32_t set_bits_mode = 0;
+    uint32_t min_count = 0;         // k-mer abundance cutoff per document (abundance_kernels.hpp); 0 / 1 = off
 };
 
 cobs_gpu_status read_params(const cobs_gpu_build_params* p, Params& out) {
@@ -72,7 +74,10 @@ cobs_gpu_status read_params(const cobs_gpu_build_params* p, Params& out) {
         if (p->struct_size < offsetof(cobs_gpu_build_params, doc_terms))
             return cobs_gpu_set_error(COBS_GPU_ERR_ARG, "cobs_gpu_build_params.struct_size is too small");
         if (p->struct_size >= offsetof(cobs_gpu_build_params, set_bits_mode)) out.doc_terms = p->doc_terms;
-        if (p->struct_size >= sizeof(cobs_gpu_build_params)) out.set_bits_mode = p->set_bits_mode;
+        if (p->struct_size >= sizeof(cobs_gpu_build_params)) {
+            out.set_bits_mode = p->set_bits_mode;
+            out.min_count = p->min_count;
+        }
         if (out.set_bits_mode > 2) return cobs_gpu_set_error(COBS_GPU_ERR_ARG, "set_bits_mode: 0, 1 or 2");
         out.term_size = p->term_size;
         out.canonicalize = p->canonicalize;
@@ -119,6 +124,8 @@ struct ArraySource final : DocSource {
 struct BuildContext {
     StagingContext sc;
     DevBuf<uint8_t>* planes = nullptr;
+    DevBuf<uint8_t>* table = nullptr;       // min_count >= 2 only: owner words, then count words (abundance_kernels.hpp)
+    int dev = 0;
     // writing an index file: the matrix of the current (sub-)index and the two pinned buffers its
     // rows leave through -- allocated once per build, not once per sub-index
     DevBuf<uint8_t> matrix;
@@ -128,9 +135,28 @@ struct BuildContext {
         if (sc.ready) return COBS_GPU_OK;
         cobs_gpu_status st = sc.init(parses);
         if (st != COBS_GPU_OK) return st;
-        int dev = 0;
         BUILD_TRY(hipGetDevice(&dev));
         planes = stage_pool().take_planes(dev);
+        return COBS_GPU_OK;
+    }
+    // the counting table of a batch of `total` text bytes, zeroed on the build stream
+    cobs_gpu_status clear_table(uint64_t total, AbundanceArgs& a) {
+        if (!table) table = stage_pool().take_table(dev);
+        if (total >> kAbundanceOffsetBits)
+            return cobs_gpu_set_error(COBS_GPU_ERR_UNSUPPORTED, "min_count: a batch of 2^40 text bytes or more; lower text_batch_bytes");
+        const uint64_t cap = abundance_capacity(total);
+        if (table->reserve((size_t)(cap * kAbundanceSlotBytes)) != hipSuccess) {
+            (void)hipGetLastError();
+            const std::string m = "min_count: no device memory for the counting table of a batch (" +
+                                  std::to_string(cap * kAbundanceSlotBytes >> 20) + " MiB for " + std::to_string(total) +
+                                  " text bytes); lower text_batch_bytes";
+            return cobs_gpu_set_error(COBS_GPU_ERR_HIP, m.c_str());
+        }
+        BUILD_TRY(hipMemsetAsync(table->p, 0, (size_t)(cap * kAbundanceSlotBytes), sc.stream));
+        a.owner = reinterpret_cast<unsigned long long*>(table->p);
+        a.count = reinterpret_cast<uint32_t*>(table->p + cap * 8);
+        a.mask = cap - 1;
+        a.total = total;
         return COBS_GPU_OK;
     }
     BuildContext() = default;
@@ -140,6 +166,7 @@ struct BuildContext {
         if (sc.copy_stream) (void)hipStreamSynchronize(sc.copy_stream);
         if (sc.stream) (void)hipStreamSynchronize(sc.stream);
         if (planes) stage_pool().give_planes(planes);
+        if (table) stage_pool().give_table(table);
     }
 };
 
@@ -203,7 +230,16 @@ cobs_gpu_status build_into(BuildContext& ctx, uint32_t* d_matrix, uint64_t sig, 
                 BUILD_TRY(hipMemsetAsync(guard.planes->p, 0, (size_t)plane_bytes, stream));
                 a.bytemap = guard.planes->p;
             }
-            BUILD_TRY(launch_build(a, total, stream));
+            if (pr.min_count >= 2) {
+                // the cutoff: count the batch's terms per document, then set the bits of those that reach it
+                AbundanceArgs ab;
+                ab.b = a;
+                ab.min_count = pr.min_count;
+                if ((bst = ctx.clear_table(total, ab)) != COBS_GPU_OK) return bst;
+                BUILD_TRY(launch_abundance(ab, stream));
+            } else {
+                BUILD_TRY(launch_build(a, total, stream));
+            }
             if (planes) {
                 PackArgs pk;
                 pk.bytemap = guard.planes->p;

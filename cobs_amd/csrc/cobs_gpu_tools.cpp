@@ -13,7 +13,8 @@
 // Flags of the two constructors: --file-type, -h/--num-hashes, -f/--false-positive-rate,
 // -k/--term-size, --no-canonicalize, -C/--clobber, --continue; -m/--memory, -T/--threads,
 // --keep-temporary, --tmp-path are accepted and ignored (there are no temporary files: the matrix
-// is built in HBM), -d/--device selects the GPU.
+// is built in HBM), -d/--device selects the GPU, --min-count N keeps a k-mer in a document only if
+// it occurs there at least N times (no reference counterpart: the reference reads cleaned .ctx files).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -61,6 +62,7 @@ struct Args {
             else if (a == "-C" || a == "--clobber") clobber = true;
             else if (a == "--continue") cont = true;
             else if (a == "-d" || a == "--device") p.device = std::atoi(need());
+            else if (a == "--min-count") p.min_count = (uint32_t)std::strtoul(need(), nullptr, 10);
             else if (a == "-m" || a == "--memory" || a == "-T" || a == "--threads" || a == "--tmp-path") (void)need();
             else if (a == "--keep-temporary") {}
             else if (!a.empty() && a[0] == '-' && a.size() > 1) { std::fprintf(stderr, "unknown flag %s\n", a.c_str()); return false; }
@@ -107,7 +109,7 @@ int construct(int argc, char** argv, bool compact) {
     Args a;
     if (!a.parse(argc, argv, compact) || a.positional.size() != 2) {
         std::fprintf(stderr, "usage: cobs_gpu_query %s INPUT OUT_FILE [--file-type T] [-h HASHES] [-f FPR] [-k K]%s "
-                             "[--no-canonicalize] [-C] [-d DEVICE]\n",
+                             "[--no-canonicalize] [-C] [-d DEVICE] [--min-count N]\n",
                      compact ? "compact-construct" : "classic-construct", compact ? " [-p PAGE_SIZE]" : "");
         return 1;
     }
@@ -115,17 +117,18 @@ int construct(int argc, char** argv, bool compact) {
     // statement for statement what src/cobs.cpp:235-241 / :373-377 do
     cobs_gpu::DocumentList filelist(a.positional[0], cobs_gpu::StringToFileType(a.file_type));
     print_document_list(filelist, a.p.term_size);
+    if (a.p.min_count > 1) std::cout << "min_count: " << a.p.min_count << std::endl;
     if (compact) {
         cobs_gpu::CompactIndexParameters p;
         p.term_size = a.p.term_size; p.canonicalize = (uint8_t)a.p.canonicalize; p.num_hashes = a.p.num_hashes;
         p.false_positive_rate = a.p.false_positive_rate; p.page_size = a.p.page_size;
-        p.clobber = a.clobber; p.continue_ = a.cont; p.device = a.p.device;
+        p.clobber = a.clobber; p.continue_ = a.cont; p.device = a.p.device; p.min_count = a.p.min_count;
         cobs_gpu::compact_construct(filelist, a.positional[1], "", p);
     } else {
         cobs_gpu::ClassicIndexParameters p;
         p.term_size = a.p.term_size; p.canonicalize = (uint8_t)a.p.canonicalize; p.num_hashes = a.p.num_hashes;
         p.false_positive_rate = a.p.false_positive_rate;
-        p.clobber = a.clobber; p.continue_ = a.cont; p.device = a.p.device;
+        p.clobber = a.clobber; p.continue_ = a.cont; p.device = a.p.device; p.min_count = a.p.min_count;
         cobs_gpu::classic_construct(filelist, a.positional[1], "", p);
     }
     return 0;

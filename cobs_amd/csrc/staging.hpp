@@ -101,16 +101,31 @@ struct StagePool {
     std::mutex mu;
     std::vector<Stage*> idle;
     std::vector<DevBuf<uint8_t>*> idle_planes;     // byte-map planes (one buffer per build in flight)
+    std::vector<DevBuf<uint8_t>*> idle_tables;     // min_count counting tables (one per build that uses the cutoff)
     int device = -1;
+    void drop_idle() {                             // mu held
+        for (Stage* s : idle) delete s;
+        idle.clear();
+        for (auto* b : idle_planes) delete b;
+        idle_planes.clear();
+        for (auto* b : idle_tables) delete b;
+        idle_tables.clear();
+    }
+    DevBuf<uint8_t>* take_table(int dev) {
+        std::lock_guard<std::mutex> g(mu);
+        if (device != dev) { drop_idle(); device = dev; }
+        if (idle_tables.empty()) return new DevBuf<uint8_t>;
+        DevBuf<uint8_t>* b = idle_tables.back();
+        idle_tables.pop_back();
+        return b;
+    }
+    void give_table(DevBuf<uint8_t>* b) {
+        std::lock_guard<std::mutex> g(mu);
+        idle_tables.push_back(b);
+    }
     DevBuf<uint8_t>* take_planes(int dev) {
         std::lock_guard<std::mutex> g(mu);
-        if (device != dev) {
-            for (Stage* s : idle) delete s;
-            idle.clear();
-            for (auto* b : idle_planes) delete b;
-            idle_planes.clear();
-            device = dev;
-        }
+        if (device != dev) { drop_idle(); device = dev; }
         if (idle_planes.empty()) return new DevBuf<uint8_t>;
         DevBuf<uint8_t>* b = idle_planes.back();
         idle_planes.pop_back();
@@ -122,20 +137,11 @@ struct StagePool {
     }
     void release_idle() {
         std::lock_guard<std::mutex> g(mu);
-        for (Stage* s : idle) delete s;
-        idle.clear();
-        for (auto* b : idle_planes) delete b;
-        idle_planes.clear();
+        drop_idle();
     }
     Stage* take(int dev) {
         std::lock_guard<std::mutex> g(mu);
-        if (device != dev) {                    // buffers belong to the device they were made on
-            for (Stage* s : idle) delete s;
-            idle.clear();
-            for (auto* b : idle_planes) delete b;
-            idle_planes.clear();
-            device = dev;
-        }
+        if (device != dev) { drop_idle(); device = dev; }     // buffers belong to the device they were made on
         if (idle.empty()) return new Stage;
         Stage* s = idle.back();
         idle.pop_back();

@@ -35,7 +35,21 @@ typedef struct cobs_gpu_build_params {
      * per-document planes that a second kernel packs into the matrix (faster than the part's
      * scattered-atomic rate; used when the planes of a batch fit 3 GiB).  Same index either way. */
     uint32_t set_bits_mode;
-    uint32_t reserved;
+    /* k-mer abundance cutoff: a term sets its bits in document d's column only if it occurs at least
+     * min_count times WITHIN document d (0 and 1 = off: no table, no extra kernel, today's bytes).
+     * Occurrences are the term positions the builder hashes (process_terms order; sequence boundaries
+     * and gap stretches respected, raw stretches included); occurrences in other documents never count.
+     * Two occurrences are the same term when the bytes handed to the hash function are equal, i.e.
+     * after canonicalisation (a k-mer and its reverse complement count together when canonicalize = 1,
+     * apart when it is 0) and after the mapping of invalid characters to 0 that goes with it.  Applies
+     * to every builder below and every document type; .ctx and .cobs_doc documents hold each k-mer
+     * once, so a cutoff of 2 or more empties them (consistent, not an error).  Sizing does not change:
+     * signature_size = 0 and the compact grouping, sort and page heuristic still use the unfiltered
+     * num_terms (sizing from kept terms would need a second pass over the corpus).  The counting table
+     * of a batch takes 12 bytes x the power of two >= 2 x its text bytes of device memory: lower
+     * text_batch_bytes if that does not fit.  Was `reserved` (size and offsets unchanged); read only
+     * when struct_size >= sizeof(cobs_gpu_build_params). */
+    uint32_t min_count;
 } cobs_gpu_build_params;
 
 /* classic_construct (construction/classic_index.cpp:565-659) for documents that are already
@@ -128,7 +142,7 @@ cobs_gpu_status cobs_gpu_build_index_list(uint32_t kind, const cobs_gpu_doclist*
                                           const cobs_gpu_options* opts, cobs_gpu_index** out);
 
 /* The builders keep their staging memory (three pinned + device text buffers of 256 MiB, the byte
- * planes) for the next build of the process; this frees what no build is using right now. */
+ * planes, the counting table of min_count) for the next build of the process; this frees what no build is using right now. */
 void cobs_gpu_build_release_buffers(void);
 
 /* classic_combine (construction/classic_index.cpp:195-327): the rows of n classic indexes with equal

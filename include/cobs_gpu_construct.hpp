@@ -136,6 +136,7 @@ struct ClassicIndexParameters {
     bool continue_ = false;
     bool keep_temporary = false;     // unused
     int device = -1;                 // which GPU builds the index (not in the reference)
+    uint32_t min_count = 1;          // k-mer abundance cutoff per document, 0 / 1 = off (not in the reference)
 };
 
 struct CompactIndexParameters {
@@ -150,6 +151,7 @@ struct CompactIndexParameters {
     bool continue_ = false;
     bool keep_temporary = false;
     int device = -1;
+    uint32_t min_count = 1;
 };
 
 namespace detail {
@@ -175,6 +177,7 @@ cobs_gpu_build_params params_of(const P& p, uint64_t signature_size, uint64_t pa
     b.signature_size = signature_size;
     b.page_size = page_size;
     b.device = p.device;
+    b.min_count = p.min_count;
     return b;
 }
 }  // namespace detail
