@@ -103,6 +103,9 @@ SYMBOLS = {
     "cobs_gpu_plant": (_int, [_vp, _sz, _cp, _sz, C.POINTER(_u32), C.POINTER(_u32), _sz, _u64]),
     "cobs_gpu_close": (None, [_vp]),
     "cobs_gpu_set_tuning": (_int, [_vp, _cp, C.c_int64]),
+    "cobs_gpu_set_invalid_bases": (_int, [_vp, _u32]),
+    "cobs_gpu_get_invalid_bases": (_int, [_vp, C.POINTER(_u32)]),
+    "cobs_gpu_batch_scored_positions": (_int, [_vp, C.c_size_t, _vp]),
     "cobs_gpu_set_findere": (_int, [_vp, _u32]),
     "cobs_gpu_get_findere": (_int, [_vp, C.POINTER(_u32)]),
     "cobs_gpu_plan_shards": (_int, [_cp, _u32, _u32, _pu64, _pu64, _pu64]),
@@ -174,6 +177,8 @@ SYMBOLS = {
     "cobs_gpu_multi_close": (None, [_vp]),
     "cobs_gpu_multi_size": (_sz, [_vp]),
     "cobs_gpu_multi_index": (_vp, [_vp, _sz]),
+    "cobs_gpu_multi_set_invalid_bases": (_int, [_vp, _u32]),
+    "cobs_gpu_multi_get_invalid_bases": (_int, [_vp, C.POINTER(_u32)]),
     "cobs_gpu_multi_set_findere": (_int, [_vp, _u32]),
     "cobs_gpu_multi_get_findere": (_int, [_vp, C.POINTER(_u32)]),
     "cobs_gpu_multi_search_batch": (_int, [_vp, C.POINTER(_cp), C.POINTER(_sz), _sz, _dbl, _sz,

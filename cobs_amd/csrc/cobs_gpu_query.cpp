@@ -29,12 +29,15 @@
 static void usage() {
     std::fprintf(stderr,
                  "usage: cobs_gpu_query -i INDEX [-i INDEX ...] [-t THRESHOLD] [-l LIMIT] "
-                 "[-d DEVICE[,DEVICE...]] [--hbm-budget GIB] [--findere Z] [--positions] (QUERY | -f QUERY_FILE)\n"
+                 "[-d DEVICE[,DEVICE...]] [--hbm-budget GIB] [--findere Z] [--invalid-bases MODE] [--positions] (QUERY | -f QUERY_FILE)\n"
                  "       --positions: every result line gets a tab and one character per position of the query in that\n"
                  "        document, position 0 first: 1 = the k-mer there (with --findere Z: all Z + 1 from there) is present;\n"
                  "        the number of 1s is the score.  Not with several devices or --hbm-budget.\n"
                  "       --findere Z (0..7): a k-mer position scores only when Z + 1 consecutive k-mers are all present\n"
                  "        (findere, beyond `cobs query`: far fewer false-positive k-mers; a query needs k + Z characters)\n"
+                 "       --invalid-bases error|miss|skip: a character outside ACGT fails the call (error, the default, as `cobs query`\n"
+                 "        does), or its k-mers count as absent (miss), or they also leave the threshold's denominator (skip:\n"
+                 "        reads with an N are answered over their valid k-mers)\n"
                  "       -d 0,1,2,3: the index is sharded by sub-index block over the listed GPUs, every search is\n"
                  "        one scan per GPU + one RCCL exchange (same results as on one GPU)\n"
                  "       (--load-complete and -T/--threads of `cobs query` are accepted and ignored: the index\n"
@@ -45,7 +48,7 @@ static void usage() {
                  "                      [--file-type T] [--canonical] [-d DEVICE]   (`cobs generate-queries`, same flags)\n"
                  "       cobs_gpu_query --benchmark -i INDEX [-k KMERS] [-q QUERIES] [-w WARMUP] [--seed S] [--dist]\n"
                  "       cobs_gpu_query benchmark-fpr INDEX [-k KMERS] [-q QUERIES] [-w WARMUP] [-d|--dist] [--seed S] [--device N[,M..]]\n"
-                 "                      [--findere Z]\n"
+                 "                      [--findere Z] [--invalid-bases MODE]\n"
                  "        (`cobs benchmark-fpr`, same flags: -d / --dist adds the distribution of all scores,\n"
                  "         RESULT name=benchmark_fpr fpr=<score> dist=<count> lines; --findere Z adds findere=Z and\n"
                  "         fpr=<scoring positions / all positions of the timed queries in all documents> to the RESULT line)\n"
@@ -200,6 +203,7 @@ int main(int argc, char** argv) {
     uint64_t synth_docs = 10000, synth_page = 0, synth_hashes = 1;
     bool bench = fpr_mode, dist = false;
     int findere = -1;                        // --findere Z; -1: not given (the handle's default, 0)
+    unsigned invalid_bases = COBS_GPU_INVALID_ERROR;   // --invalid-bases MODE
     bool positions = false;                  // --positions
     unsigned num_kmers = 1000, num_queries = 10000, num_warmup = 100;
     size_t seed = std::random_device{}();
@@ -248,6 +252,13 @@ int main(int argc, char** argv) {
             if (v.empty() || *end != '\0' || z < 0 || z > 7) { std::fprintf(stderr, "--findere: 0 .. 7\n"); return 1; }
             findere = (int)z;
         }
+        else if (a == "--invalid-bases") {
+            const std::string v = need("--invalid-bases");
+            if (v == "error") invalid_bases = COBS_GPU_INVALID_ERROR;
+            else if (v == "miss") invalid_bases = COBS_GPU_INVALID_MISS;
+            else if (v == "skip") invalid_bases = COBS_GPU_INVALID_SKIP;
+            else { std::fprintf(stderr, "--invalid-bases: error, miss or skip\n"); return 1; }
+        }
         else if (a == "--positions") positions = true;
         else if (a == "-h" || a == "--help") { usage(); return 0; }
         else if (!a.empty() && a[0] == '-') { std::fprintf(stderr, "unknown flag %s\n", a.c_str()); usage(); return 1; }
@@ -273,11 +284,13 @@ int main(int argc, char** argv) {
             auto* sh = new cobs_gpu::ShardedClassicSearch(index_paths, devices.empty() ? std::vector<int>{0} : devices, hbm_budget);
             std::unique_ptr<cobs_gpu::BatchSearch> keep(sh);
             if (findere > 0) sh->set_findere((unsigned)findere);
+            if (invalid_bases != COBS_GPU_INVALID_ERROR) sh->set_invalid_bases(invalid_bases);
             return keep;
         }
         auto* cs = new cobs_gpu::ClassicSearch(index_paths, device, hbm_budget);
         std::unique_ptr<cobs_gpu::BatchSearch> keep(cs);
         if (findere > 0) cs->set_findere((unsigned)findere);
+        if (invalid_bases != COBS_GPU_INVALID_ERROR) cs->set_invalid_bases(invalid_bases);
         return keep;
     };
     if (!random_out.empty()) {

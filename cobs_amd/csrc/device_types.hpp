@@ -36,6 +36,20 @@ struct HashArgs {
     uint32_t canonicalize;
     uint32_t num_hashes;
     uint32_t idx64;             // some sub-index has >= 2^32 - 1 rows: 64-bit table entries
+    // cobs_gpu_set_invalid_bases (canonicalize != 0 only): 0 = a non-ACGT character fails the query (err_query);
+    // otherwise a term that holds one names the zero row of every sub-index, like a padding term, and err_query stays
+    uint32_t invalid_bases;
+    uint32_t findere;           // z of the pass: a scored position p < T - z is valid when its k + z characters are
+    uint32_t* valid;            // [nq] valid scored positions per query (zeroed; one atomic per wave and query), or nullptr
+};
+
+// ceil(threshold * V) per query from K1's valid positions (invalid_bases = skip): the thresholds of a file follow the
+// CONTENT of the queries, so they are made on the device behind K1 -- a replayed graph gets them right by itself.
+struct SkipThresholdArgs {
+    const uint32_t* valid;      // [nq]
+    uint32_t* thresholds;       // [nq]
+    double threshold;           // > 0
+    uint32_t nq;
 };
 
 // One selected (query, document) pair of the on-device threshold pass.

@@ -634,6 +634,19 @@ cobs_gpu_status cobs_gpu_get_findere(const cobs_gpu_index* ix, uint32_t* z) {
     return COBS_GPU_OK;
 }
 
+cobs_gpu_status cobs_gpu_set_invalid_bases(cobs_gpu_index* ix, uint32_t mode) {
+    if (!ix) return fail(COBS_GPU_ERR_ARG, "NULL argument");
+    if (mode > (uint32_t)COBS_GPU_INVALID_SKIP) return fail(COBS_GPU_ERR_ARG, "invalid_bases: 0 (error), 1 (miss) or 2 (skip)");
+    ix->invalid_bases = mode;
+    return COBS_GPU_OK;
+}
+
+cobs_gpu_status cobs_gpu_get_invalid_bases(const cobs_gpu_index* ix, uint32_t* mode) {
+    if (!ix || !mode) return fail(COBS_GPU_ERR_ARG, "NULL argument");
+    *mode = ix->invalid_bases;
+    return COBS_GPU_OK;
+}
+
 size_t cobs_gpu_num_files(const cobs_gpu_index* ix) { return ix ? ix->parts.size() : 0; }
 
 cobs_gpu_status cobs_gpu_info(const cobs_gpu_index* ix, size_t f, cobs_gpu_index_info* o) {

@@ -272,6 +272,7 @@ struct cobs_gpu_index {
     uint64_t hbm_budget = 0;      // 0 = everything resident
     uint32_t waves_per_group = 0; // 0 = by query length
     uint32_t findere = 0;         // cobs_gpu_set_findere: z (0..7); every batch samples it when it runs
+    uint32_t invalid_bases = 0;   // cobs_gpu_set_invalid_bases: COBS_GPU_INVALID_ERROR / _MISS / _SKIP; sampled like findere
     cobs_amd::Tuning tune;
     std::vector<cobs_amd::Part> parts;
     cobs_amd::StreamBufs stream;
@@ -309,6 +310,12 @@ struct cobs_gpu_batch {
     int planes = 0;
     uint64_t max_terms = 0;              // longest query of the batch, in terms
     uint32_t findere = 0;                // z of the current / last run (the handle's, sampled by set_run_state)
+    uint32_t invalid_bases = 0;          // ... and its invalid-bases policy
+    // invalid_bases != error: K1 counts every query's valid scored positions per file, [file][nq]; they come home when the
+    // flag words do (fetch_valid) and serve cobs_gpu_batch_scored_positions and the host-side thresholds of `skip`
+    cobs_amd::DevBuf<uint32_t> valid;
+    std::vector<uint32_t> h_valid;
+    bool valid_home = false;
     cobs_amd::DevBuf<cobs_amd::HitDev> hits;
     cobs_amd::DevBuf<uint2> topk_out;    // K3 output [file][query][k], ordered (score desc, doc asc)
     cobs_amd::DevBuf<uint32_t> topk_cnt; // [file][query]
@@ -456,6 +463,11 @@ cobs_gpu_status run_impl(cobs_gpu_batch* b, double threshold, size_t topk, void*
 cobs_gpu_status set_queries_on(cobs_gpu_batch* b, const char* const* queries, const size_t* lens, size_t nq,
                                hipStream_t up, bool wait, size_t* bad_query, size_t index_base = 0);
 uint32_t threshold_for(double threshold, uint64_t terms);
+// the threshold of query q in file f under the batch's invalid-bases policy: ceil(t * (T - z)), or -- skip, valid after a
+// sync -- ceil(t * V), at least 1 when t > 0 (skip_thresholds_kernel computes the same on the device)
+uint32_t threshold_of(const cobs_gpu_batch* b, size_t q, size_t f);
+// K1's valid positions of the last run to b->h_valid (policy != error; the run has finished: the caller waited for it)
+cobs_gpu_status fetch_valid(cobs_gpu_batch* b);
 uint64_t total_hashes(const cobs_gpu_batch* b, size_t q);
 // positions query q scores in file p: its terms T = |q| - k + 1, less the batch's findere z (windows of z + 1 terms)
 uint64_t scored_positions(const cobs_gpu_batch* b, size_t q, const Part& p);

@@ -394,12 +394,17 @@ hipError_t launch_remap_rows(const RemapArgs& a, uint64_t entries, bool idx64, h
 // flags instead of zeros (ROCm 7.2, MI355X; the pass then reported "invalid base pair in query 998395903" for a
 // valid query -- found by tests/test_gpu_fuzz.py::test_random_ties under COBS_FUZZ_SEED=14).  A kernel node carries
 // its arguments by value.
-__global__ void clear_flags_kernel(uint32_t* flags) {
-    if (threadIdx.x < 4u) flags[threadIdx.x] = 0u;
+// `valid` (K1's per-query counters of valid positions, cobs_gpu_set_invalid_bases) is cleared here for the same reason.
+__global__ void clear_flags_kernel(uint32_t* flags, uint32_t* valid, uint32_t nvalid) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < 4u) flags[i] = 0u;
+    if (i < nvalid) valid[i] = 0u;
 }
 
-hipError_t launch_clear_flags(uint32_t* flags, hipStream_t stream) {
-    hipLaunchKernelGGL(clear_flags_kernel, dim3(1), dim3(64), 0, stream, flags);
+hipError_t launch_clear_flags(uint32_t* flags, hipStream_t stream, uint32_t* valid, uint32_t nvalid) {
+    if (valid == nullptr) nvalid = 0;
+    const uint32_t threads = nvalid ? 256u : 64u;
+    hipLaunchKernelGGL(clear_flags_kernel, dim3(std::max(1u, (nvalid + threads - 1u) / threads)), dim3(threads), 0, stream, flags, valid, nvalid);
     return hipGetLastError();
 }
 

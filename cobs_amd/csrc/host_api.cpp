@@ -69,6 +69,7 @@ static cobs_gpu_status host_pass_begin(cobs_gpu_index* ix, int slot, const char*
     for (const auto& p : ix->parts) any_streamed = any_streamed || p.streamed;
     if (nq > 0 && nq <= 16 && ix->tune.graph != 0 && !any_streamed && !ix->tune.phase_slots) {
         b->findere = ix->findere;            // (the shape class holds it; run_impl samples the same)
+        b->invalid_bases = ix->invalid_bases;
         // the shape class of the pass and every address the captured nodes hold
         auto make_key = [&]() {
             uint64_t key = 1469598103934665603ull;
@@ -81,6 +82,7 @@ static cobs_gpu_status host_pass_begin(cobs_gpu_index* ix, int slot, const char*
             mixin((uint64_t)(uintptr_t)b->text.p); mixin((uint64_t)(uintptr_t)b->counts.p); mixin((uint64_t)(uintptr_t)b->hits.p);
             mixin((uint64_t)(uintptr_t)b->topk_out.p); mixin((uint64_t)(uintptr_t)b->topk_cnt.p); mixin((uint64_t)(uintptr_t)b->cand.p);
             for (auto& w : b->work) { mixin((uint64_t)(uintptr_t)w.table.p); mixin((uint64_t)(uintptr_t)w.thr.p); }
+            mixin((uint64_t)(uintptr_t)b->valid.p);
             mixin((uint64_t)(uintptr_t)b->h_res.p); mixin((uint64_t)(uintptr_t)b->h_rows.p);      // the graph writes there
             mixin((uint64_t)(uintptr_t)b->h_text.p); mixin((uint64_t)(uintptr_t)b->h_thr_stage.p);
             mixin(ix->tune.waves); mixin(ix->tune.tile_w); mixin((uint64_t)(int64_t)ix->tune.mq); mixin(ix->tune.lds_staged);
@@ -229,7 +231,8 @@ static cobs_gpu_status host_pass_end(cobs_gpu_index* ix, int slot, double thresh
         HIP_TRY(hipEventSynchronize(b->done));
         std::memcpy(b->h_flags, b->h_flags_pin.p, sizeof b->h_flags);
         b->synced = true;
-        st = COBS_GPU_OK;
+        st = fetch_valid(b);
+        if (st != COBS_GPU_OK) return st;
         if (b->h_flags[0] != 0u) {           // K1 keeps 2^32-1 - (first query with a non-ACGT character)
             if (bad_query) *bad_query = 0xFFFFFFFFu - b->h_flags[0];
             st = fail(COBS_GPU_ERR_INVALID_BASE, "Invalid DNA base pair in query string. Only ACGT are allowed. (query " +

@@ -36,6 +36,43 @@ namespace cobs_amd {
 // ---------------------------------------------------------------------------
 // K1: one thread per query position (canonicalisation and XXH64: term_hash.hpp).
 
+// invalid_bases != 0.  The z characters behind term i's k-mer (`tail`): position i < T - z scores the terms i .. i + z, so it
+// is valid when they hold valid characters too (findere; z = 0: nothing to look at).
+__device__ __forceinline__ bool window_tail_valid(const uint8_t* tail, uint32_t i, uint32_t T, uint32_t z) {
+    if (i + z >= T) return false;               // no window of z + 1 terms starts here: not a scored position
+    uint32_t good = 1u;
+    for (uint32_t s = 0; s < z; ++s) good &= fwd_base(tail[s]) != 0 ? 1u : 0u;
+    return good != 0;
+}
+
+// valid[q] += the lanes of this wave that hold a valid position of query q.  A thread per position of 10 000 reads would be
+// ten million atomics onto ten thousand addresses: the lanes of a wave that share a query (a query's span is a multiple of
+// 8 threads, so a wave sees at most eight) are counted by a ballot first, and one lane adds the sum.  Called by every lane
+// that is still active, with converged control flow.
+__device__ __forceinline__ void add_valid_position(uint32_t* valid, uint32_t q, bool ok) {
+    const uint32_t lane = __lane_id();
+    bool pending = true;
+    for (;;) {
+        const uint64_t waiting = __ballot(pending);
+        if (waiting == 0) break;
+        const uint32_t leader = (uint32_t)__ffsll((unsigned long long)waiting) - 1u;
+        const uint32_t lq = (uint32_t)__shfl((int)q, (int)leader);
+        const bool mine = pending && q == lq;
+        const uint64_t votes = __ballot(mine && ok);
+        if (mine) pending = false;
+        if (lane == leader && votes != 0) atomicAdd(valid + lq, (uint32_t)__popcll(votes));
+    }
+}
+
+// invalid_bases = skip: the thresholds of one file from K1's valid positions, ceil(threshold * V) in double as the host's
+// threshold_for computes it -- and at least 1: a query without a valid position matches nothing, not everything.
+__global__ __launch_bounds__(256) void skip_thresholds_kernel(SkipThresholdArgs a) {
+    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= a.nq) return;
+    const double v = ceil(a.threshold * (double)a.valid[q]);
+    a.thresholds[q] = !(v >= 1.0) ? 1u : v >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)v;
+}
+
 template <typename IdxT>
 __global__ __launch_bounds__(256) void hash_kernel(HashArgs a, uint64_t total_threads) {
     const uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -57,7 +94,9 @@ __global__ __launch_bounds__(256) void hash_kernel(HashArgs a, uint64_t total_th
     // canonicalize == 1: any character outside ACGT makes the query invalid
     // (the reference dies, classic_search.cpp:93-96).  Every character of a
     // query of length >= k lies in some k-mer.
-    if (a.canonicalize != 0 && i < len) {
+    // (invalid_bases != 0: such a character only takes the terms that hold it out of the count, below)
+    const bool lenient = a.canonicalize != 0 && a.invalid_bases != 0;
+    if (a.canonicalize != 0 && !lenient && i < len) {
         if (fwd_base(text[i]) == 0) atomicMax(a.err_query, 0xFFFFFFFFu - q);   // first bad query wins
     }
 
@@ -72,7 +111,17 @@ __global__ __launch_bounds__(256) void hash_kernel(HashArgs a, uint64_t total_th
     const uint32_t blk = i >> 3, sub = i & 7u;
     IdxT* out = reinterpret_cast<IdxT*>(a.table) + ((b0 + q) * a.npages) * (8ull * H);
 
-    if (i >= T) {       // padding term: the all-zero row of every sub-index
+    bool term_ok = true;
+    if (lenient) {
+        if (i < T) {
+            uint32_t good = 1u;
+            for (uint32_t s = 0; s < k; ++s) good &= fwd_base(text[i + s]) != 0 ? 1u : 0u;
+            term_ok = good != 0;
+        }
+        if (a.valid != nullptr) add_valid_position(a.valid, q, i < T && term_ok && window_tail_valid(text + i + k, i, T, a.findere));
+    }
+
+    if (i >= T || !term_ok) {       // padding term (or one that holds an invalid character): the all-zero row of every sub-index
         for (uint32_t p = 0; p < a.npages; ++p) {
             const IdxT zr = (IdxT)a.pages[p].sig;
             IdxT* o = out + ((uint64_t)p * tblk + blk) * (8ull * H) + sub;
@@ -122,7 +171,8 @@ __global__ __launch_bounds__(256) void hash_kernel_k31(HashArgs a, uint64_t tota
     const uint32_t i = (uint32_t)(gid - qbase);
     const uint32_t len = a.q_len[q];
     const uint8_t* text = a.text + qbase;
-    if (a.canonicalize != 0 && i < len) {
+    const bool lenient = a.canonicalize != 0 && a.invalid_bases != 0;
+    if (a.canonicalize != 0 && !lenient && i < len) {
         if (fwd_base(text[i]) == 0) atomicMax(a.err_query, 0xFFFFFFFFu - q);   // first bad query wins
     }
     const uint64_t b0 = a.blk_off[q];
@@ -133,17 +183,9 @@ __global__ __launch_bounds__(256) void hash_kernel_k31(HashArgs a, uint64_t tota
     const uint32_t H = a.num_hashes;
     const uint32_t blk = i >> 3, sub = i & 7u;
     IdxT* out = reinterpret_cast<IdxT*>(a.table) + ((b0 + q) * a.npages) * (8ull * H);
-    if (i >= T) {
-        for (uint32_t p = 0; p < a.npages; ++p) {
-            const IdxT zr = (IdxT)a.pages[p].sig;
-            IdxT* o = out + ((uint64_t)p * tblk + blk) * (8ull * H) + sub;
-            for (uint32_t j = 0; j < H; ++j) o[j * 8] = zr;
-        }
-        return;
-    }
     // the k-mer and one following byte as 8 (unaligned) dwords; the text buffer is padded
     uint32_t f[8];
-    {
+    if (i < T) {
         const uint8_t* p = text + i;
         const uint32_t mis = (uint32_t)((uintptr_t)p & 3u);
         const uint32_t* w = reinterpret_cast<const uint32_t*>(p - mis);
@@ -153,8 +195,27 @@ __global__ __launch_bounds__(256) void hash_kernel_k31(HashArgs a, uint64_t tota
 #pragma unroll
         for (int j = 0; j < 8; ++j)
             f[j] = mis == 0 ? r[j] : (uint32_t)(((uint64_t)r[j] | ((uint64_t)r[j + 1] << 32)) >> (8 * mis));
+        f[7] &= 0x00FFFFFFu;                      // byte 31 is not part of the 31-mer
     }
-    f[7] &= 0x00FFFFFFu;                          // byte 31 is not part of the 31-mer
+    bool term_ok = true;
+    if (lenient) {
+        if (i < T) {
+            // (the masked top byte of f[7] stands in as an 'A': the character behind the k-mer does not decide on it)
+            bool good = all_acgt(f[7] | 0x41000000u);
+#pragma unroll
+            for (int j = 0; j < 7; ++j) good = good && all_acgt(f[j]);
+            term_ok = good;
+        }
+        if (a.valid != nullptr) add_valid_position(a.valid, q, i < T && term_ok && window_tail_valid(text + i + 31u, i, T, a.findere));
+    }
+    if (i >= T || !term_ok) {
+        for (uint32_t p = 0; p < a.npages; ++p) {
+            const IdxT zr = (IdxT)a.pages[p].sig;
+            IdxT* o = out + ((uint64_t)p * tblk + blk) * (8ull * H) + sub;
+            for (uint32_t j = 0; j < H; ++j) o[j * 8] = zr;
+        }
+        return;
+    }
     uint32_t c[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) c[j] = f[j];
@@ -1891,6 +1952,12 @@ hipError_t launch_hash(const HashArgs& a, uint64_t total_threads, hipStream_t st
         if (a.idx64) hipLaunchKernelGGL(hash_kernel<uint64_t>, dim3((uint32_t)blocks), dim3(256), 0, stream, a, total_threads);
         else hipLaunchKernelGGL(hash_kernel<uint32_t>, dim3((uint32_t)blocks), dim3(256), 0, stream, a, total_threads);
     }
+    return hipGetLastError();
+}
+
+hipError_t launch_skip_thresholds(const SkipThresholdArgs& a, hipStream_t stream) {
+    if (a.nq == 0) return hipSuccess;
+    hipLaunchKernelGGL(skip_thresholds_kernel, dim3((a.nq + 255u) / 256u), dim3(256), 0, stream, a);
     return hipGetLastError();
 }
 

@@ -10,6 +10,7 @@ namespace cobs_amd {
 
 // K1: one thread per query position (total_threads = span_off[nq]).
 hipError_t launch_hash(const HashArgs& a, uint64_t total_threads, hipStream_t stream);
+hipError_t launch_skip_thresholds(const SkipThresholdArgs& a, hipStream_t stream);
 
 // Smallest instantiated plane count that can hold counts up to max_terms
 // (4, 8 -> u8 scores as the reference's T < 255 path; 10, 12, 16 -> u16; 20, 24, 32 -> u32); -1 if none.
@@ -51,7 +52,7 @@ hipError_t launch_add_scores(const AddScoresArgs& a, hipStream_t stream);
 hipError_t launch_select_rows(const SelectRowsArgs& a, hipStream_t stream);
 // a row-range unit's in-range terms per query: a compact second table + its block offsets (count, scan, write)
 hipError_t launch_compact_terms(const CompactArgs& a, hipStream_t stream);
-hipError_t launch_clear_flags(uint32_t* flags, hipStream_t stream);
+hipError_t launch_clear_flags(uint32_t* flags, hipStream_t stream, uint32_t* valid = nullptr, uint32_t nvalid = 0);
 
 // Owner-routed hit exchange (xchg_kernels.hip): count == true -> records per owner into a.cursor, else scatter.
 hipError_t launch_bucket_hits(const BucketArgs& a, bool count, hipStream_t stream);

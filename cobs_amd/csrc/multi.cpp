@@ -217,6 +217,19 @@ cobs_gpu_status cobs_gpu_multi_get_findere(const cobs_gpu_multi* m, uint32_t* z)
     return cobs_gpu_get_findere(m->ranks[0].ix, z);
 }
 
+cobs_gpu_status cobs_gpu_multi_set_invalid_bases(cobs_gpu_multi* m, uint32_t mode) {
+    if (!m || m->ranks.empty()) return fail(COBS_GPU_ERR_ARG, "NULL argument");
+    // (the only way a shard refuses is a bad mode, which the first one reports before any has changed)
+    for (const auto& r : m->ranks)
+        if (cobs_gpu_status s = cobs_gpu_set_invalid_bases(r.ix, mode); s != COBS_GPU_OK) return s;
+    return COBS_GPU_OK;
+}
+
+cobs_gpu_status cobs_gpu_multi_get_invalid_bases(const cobs_gpu_multi* m, uint32_t* mode) {
+    if (!m || m->ranks.empty()) return fail(COBS_GPU_ERR_ARG, "NULL argument");
+    return cobs_gpu_get_invalid_bases(m->ranks[0].ix, mode);
+}
+
 cobs_gpu_status cobs_gpu_multi_search_batch(cobs_gpu_multi* m, const char* const* queries, const size_t* lens, size_t nq,
                                             double threshold, size_t num_results, cobs_gpu_hit* hits, size_t cap,
                                             size_t* hit_offsets, size_t* bad_query) {

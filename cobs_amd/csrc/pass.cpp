@@ -62,6 +62,25 @@ uint32_t threshold_for(double threshold, uint64_t terms) {
     return (uint32_t)v;
 }
 
+uint32_t threshold_of(const cobs_gpu_batch* b, size_t q, size_t f) {
+    const Part& p = b->ix->parts[f];
+    if (b->invalid_bases != COBS_GPU_INVALID_SKIP || p.meta.canonicalize == 0 || !b->valid_home)
+        return threshold_for(b->threshold, scored_positions(b, q, p));
+    // invalid positions leave the denominator; a query without a valid one matches nothing (not everything)
+    const uint32_t thr = threshold_for(b->threshold, b->h_valid[f * b->nq + q]);
+    return b->threshold > 0.0 ? std::max(thr, 1u) : 0u;
+}
+
+cobs_gpu_status fetch_valid(cobs_gpu_batch* b) {
+    b->valid_home = false;
+    if (b->invalid_bases == COBS_GPU_INVALID_ERROR || b->nq == 0) return COBS_GPU_OK;
+    const size_t n = b->nq * b->ix->parts.size();
+    b->h_valid.resize(n);
+    HIP_TRY(hipMemcpy(b->h_valid.data(), b->valid.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    b->valid_home = true;
+    return COBS_GPU_OK;
+}
+
 
 }  // namespace cobs_amd
 
@@ -106,6 +125,8 @@ cobs_gpu_status cobs_amd::set_queries_on(cobs_gpu_batch* b, const char* const* q
     b->ran = false;
     b->nq = 0;
     b->findere = ix->findere;         // (run_impl samples it again: a batch runs with the z of its handle at that time)
+    b->invalid_bases = ix->invalid_bases;
+    b->valid_home = false;
     if (nq >= 0xFFFFFFFEull) return fail(COBS_GPU_ERR_ARG, "too many queries");
     // reference checks, classic_search.cpp:431-433 and :453-504
     uint32_t max_term = 0, min_term = 0xFFFFFFFFu;
@@ -206,6 +227,8 @@ cobs_gpu_status cobs_amd::set_queries_on(cobs_gpu_batch* b, const char* const* q
     // (tuning key hit_cap lowers the cap the kernels honour, never raises it past the allocation)
     b->hit_cap = (uint32_t)(ix->tune.hit_cap ? std::min<uint64_t>(b->hits.cap, ix->tune.hit_cap) : b->hits.cap);
     HIP_TRY(b->h_thr_stage.reserve(std::max<size_t>(nq * ix->parts.size(), 1)));
+    // (allocated whatever the policy: a captured graph holds its address, and the policy may change between runs)
+    HIP_TRY(b->valid.reserve(nq <= 16 ? 16 * ix->parts.size() : nq * ix->parts.size()));
     b->stats[0] = algo_bytes + (uint64_t)nq * ix->local_counts * b->elem_bytes;      // until a run says otherwise
     b->stats[1] = 0;
     b->stats[2] = lookups;
@@ -238,6 +261,7 @@ uint64_t cobs_amd::pass_shape_class(const cobs_gpu_batch* b) {
     for (size_t q = 0; q < nq && !single; ++q) single = total_hashes(b, q) <= 1;
     mixin(single);
     mixin(b->findere);             // a kernel argument of the captured scan (and its instantiation)
+    mixin(b->invalid_bases);       // ... the policy one of K1, and `skip` makes its thresholds on the device
     mixin(b->hit_cap);             // ... and so is the pool's cap
     for (size_t f = 0; f < ix->parts.size() && nq; ++f) {
         const Part& p = ix->parts[f];
@@ -265,6 +289,8 @@ void cobs_amd::set_run_state(cobs_gpu_batch* b, double threshold, size_t topk, b
     b->graph_run = false;
     b->threshold = threshold;
     b->findere = ix->findere;
+    b->invalid_bases = ix->invalid_bases;
+    b->valid_home = false;
     // K3 (exact top-k on the device, every score width) needs a bounded k
     const bool use_topk = topk > 0 && topk <= 65536 &&
                           (uint64_t)topk * std::max<size_t>(b->nq, 1) * ix->parts.size() <= (1ull << 27);
@@ -337,8 +363,13 @@ cobs_gpu_status cobs_amd::run_impl(cobs_gpu_batch* b, double threshold, size_t t
         if (b->run_seq) HIP_TRY(hipStreamWaitEvent(hs, b->run_done, 0));
     }
     // device flags: first invalid query = none, selected hits = 0
-    HIP_TRY(launch_clear_flags(b->flags.p, hs));      // (a kernel: a captured memset node is not safe to replay, fetch_kernels.hip)
-    if (need_thr) {
+    // (a kernel: a captured memset node is not safe to replay, fetch_kernels.hip)
+    const bool count_valid = b->invalid_bases != COBS_GPU_INVALID_ERROR && nq;
+    // invalid_bases = skip: a file's thresholds follow the content of the queries -- made on the device right behind its K1
+    // (no host staging: a replayed graph serves other text of its shape class)
+    const bool skip_thr = need_thr && b->invalid_bases == COBS_GPU_INVALID_SKIP;
+    HIP_TRY(launch_clear_flags(b->flags.p, hs, count_valid ? b->valid.p : nullptr, count_valid ? (uint32_t)(nq * ix->parts.size()) : 0u));
+    if (need_thr && !skip_thr) {
         stage_thresholds(b, threshold);
         for (size_t f = 0; f < ix->parts.size(); ++f)
             if (nq) HIP_TRY(hipMemcpyAsync(b->work[f].thr.p, b->h_thr_stage.p + f * nq, 4 * nq, hipMemcpyHostToDevice, st));
@@ -396,9 +427,25 @@ cobs_gpu_status cobs_amd::run_impl(cobs_gpu_batch* b, double threshold, size_t t
         ha.canonicalize = p.meta.canonicalize;
         ha.num_hashes = (uint32_t)p.meta.num_hashes;
         ha.idx64 = p.idx64 ? 1u : 0u;
+        ha.invalid_bases = b->invalid_bases;
+        ha.findere = b->findere;
+        ha.valid = count_valid ? b->valid.p + f * nq : nullptr;
         // (the kernel bounds itself by span_off[nq] on the device; the grid is rounded up so that a
         // captured launch serves every batch of its shape class)
         HIP_TRY(launch_hash(ha, round_up(b->span_off[nq], 1024), hs));
+        if (skip_thr) {
+            SkipThresholdArgs ta;
+            if (p.meta.canonicalize != 0) {
+                ta.valid = b->valid.p + f * nq;
+                ta.thresholds = b->work[f].thr.p;
+                ta.threshold = threshold;
+                ta.nq = (uint32_t)nq;
+                HIP_TRY(launch_skip_thresholds(ta, hs));
+            } else {     // every byte of such a file is a valid character: the nominal thresholds
+                for (size_t q = 0; q < nq; ++q) b->h_thr_stage.p[f * nq + q] = threshold_for(threshold, scored_positions(b, q, p));
+                HIP_TRY(hipMemcpyAsync(b->work[f].thr.p, b->h_thr_stage.p + f * nq, 4 * nq, hipMemcpyHostToDevice, st));
+            }
+        }
         if (cnt_off[f + 1] > cnt_off[f]) {
             // how many rows the batch looks up in every streamed piece of this file (one counter per whole slice / row range)
             CountArgs ca;
@@ -976,6 +1023,7 @@ cobs_gpu_status cobs_gpu_batch_sync(cobs_gpu_batch* b, void* hip_stream, size_t*
         HIP_TRY(hipStreamSynchronize(st));
     }
     b->synced = true;
+    if (cobs_gpu_status vs = fetch_valid(b); vs != COBS_GPU_OK) return vs;
     if (b->h_flags[0] != 0u) {           // K1 keeps 2^32-1 - (first query with a non-ACGT character)
         const uint32_t bad = 0xFFFFFFFFu - b->h_flags[0];
         if (bad_query) *bad_query = bad;
@@ -986,6 +1034,17 @@ cobs_gpu_status cobs_gpu_batch_sync(cobs_gpu_batch* b, void* hip_stream, size_t*
     return COBS_GPU_OK;
 }
 
+
+cobs_gpu_status cobs_gpu_batch_scored_positions(const cobs_gpu_batch* b, size_t file, uint32_t* out) {
+    if (!b || (!out && b->nq)) return fail(COBS_GPU_ERR_ARG, "NULL argument");
+    if (file >= b->ix->parts.size()) return fail(COBS_GPU_ERR_ARG, "bad file number");
+    if (!b->ran || !b->synced) return fail(COBS_GPU_ERR_ARG, "run and sync the batch first");
+    const Part& p = b->ix->parts[file];
+    const bool counted = b->invalid_bases != COBS_GPU_INVALID_ERROR && p.meta.canonicalize != 0 && b->valid_home;
+    for (size_t q = 0; q < b->nq; ++q)
+        out[q] = counted ? b->h_valid[file * b->nq + q] : (uint32_t)scored_positions(b, q, p);
+    return COBS_GPU_OK;
+}
 
 cobs_gpu_status cobs_gpu_batch_phase_stamps(cobs_gpu_batch* b, uint64_t* out, size_t cap_words, size_t* n_words) {
     if (!b || !n_words) return fail(COBS_GPU_ERR_ARG, "NULL argument");

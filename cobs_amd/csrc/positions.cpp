@@ -131,6 +131,9 @@ cobs_gpu_status run_pass(const Call& c, const std::vector<size_t>& qsel) {
         ha.canonicalize = p.meta.canonicalize;
         ha.num_hashes = (uint32_t)p.meta.num_hashes;
         ha.idx64 = p.idx64 ? 1u : 0u;
+        ha.invalid_bases = ix->invalid_bases;     // (miss / skip: a position whose window holds an invalid character reads 0)
+        ha.findere = c.z;
+        ha.valid = nullptr;
         HIP_TRY(launch_hash(ha, round_up(b->span_off[n], 1024), st));
     }
     HIP_TRY(hipEventRecord(w->ev[1], st));

@@ -121,7 +121,7 @@ static cobs_gpu_status rank_raw(const cobs_gpu_batch* b, size_t q, const uint8_t
     size_t passing = 0;
     for (size_t f = 0; f < ix->parts.size(); ++f) {
         const Part& p = ix->parts[f];
-        const uint32_t thr = threshold_for(b->threshold, scored_positions(b, q, p));
+        const uint32_t thr = threshold_of(b, q, f);
         const uint64_t d0 = glob ? 0 : p.slot_begin;
         const uint64_t d1 = glob ? p.meta.doc_names.size()
                                  : std::min<uint64_t>(p.slot_begin + p.slot_count, p.meta.doc_names.size());
@@ -146,7 +146,7 @@ static cobs_gpu_status rank_raw(const cobs_gpu_batch* b, size_t q, const uint8_t
     // pass 2: scatter in (file, doc) order; positions >= want are dropped
     for (size_t f = 0; f < ix->parts.size(); ++f) {
         const Part& p = ix->parts[f];
-        const uint32_t thr = threshold_for(b->threshold, scored_positions(b, q, p));
+        const uint32_t thr = threshold_of(b, q, f);
         const uint64_t d0 = glob ? 0 : p.slot_begin;
         const uint64_t d1 = glob ? p.meta.doc_names.size()
                                  : std::min<uint64_t>(p.slot_begin + p.slot_count, p.meta.doc_names.size());
@@ -477,7 +477,7 @@ static cobs_gpu_status hits_host_impl(cobs_gpu_batch* b, size_t q, size_t num_re
         if (st != COBS_GPU_OK) return st;
         for (size_t f = 0; f < ix->parts.size(); ++f) {
             const Part& p = ix->parts[f];
-            const uint32_t thr = threshold_for(b->threshold, scored_positions(b, q, p));
+            const uint32_t thr = threshold_of(b, q, f);
             // only documents whose slots this shard computed
             const uint64_t d0 = b->view_global ? 0 : p.slot_begin;
             const uint64_t d1 = b->view_global ? p.meta.doc_names.size()

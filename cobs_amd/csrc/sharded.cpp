@@ -73,7 +73,8 @@ cobs_gpu_status meta_wait(cobs_gpu_batch* b, cobs_gpu_comm* c, Agreed* a) {
     b->h_flags[1] = 0;
     b->h_flags[2] = (uint32_t)mine[2];
     b->h_flags[3] = (uint32_t)(mine[2] >> 32);
-    return COBS_GPU_OK;
+    // (the record was packed behind the pass's kernels: K1's valid positions are final)
+    return fetch_valid(b);
 }
 
 cobs_gpu_status make_scratch(cobs_gpu_index* ix, int slot) {

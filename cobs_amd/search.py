@@ -103,33 +103,50 @@ def _options(device, shard_rank, shard_count, hbm_budget=0, shard_mode=0):
     return o
 
 
+INVALID_BASES = ("error", "miss", "skip")     # COBS_GPU_INVALID_ERROR / _MISS / _SKIP
+
+
+def _invalid_bases_mode(mode):
+    if isinstance(mode, str) and mode in INVALID_BASES:
+        return INVALID_BASES.index(mode)
+    if not isinstance(mode, str) and mode in (0, 1, 2):
+        return int(mode)
+    raise ValueError("invalid_bases: 'error', 'miss' or 'skip'")
+
+
 class Search:
     """cobs_index.Search: open one or several index files (classic or compact,
     auto-detected per file) and query them on the GPU."""
 
     def __init__(self, path, device=-1, shard_rank=0, shard_count=1, hbm_budget=0, shard_mode=0, _handle=None,
-                 findere=0):
+                 invalid_bases="error", findere=0):
         self._lib = _capi.load()
         self._h = C.c_void_p()
+        mode = _invalid_bases_mode(invalid_bases)
         if _handle is not None:
             self._h = _handle
             if findere:
                 self.set_findere(findere)
+            if mode:
+                self.invalid_bases = mode
             return
         paths = [path] if isinstance(path, (str, bytes, os.PathLike)) else list(path)
         arr = (C.c_char_p * len(paths))(*[os.fsencode(p) for p in paths])
         opts = _options(device, shard_rank, shard_count, hbm_budget, shard_mode)
         check(self._lib.cobs_gpu_open(arr, len(paths), C.byref(opts), C.byref(self._h)))
-        if findere:
-            try:
+        try:
+            if findere:
                 self.set_findere(findere)
-            except Exception:
-                self.close()
-                raise
+            if mode:
+                self.invalid_bases = mode
+        except Exception:
+            self.close()
+            raise
 
     @classmethod
     def synthetic(cls, kind, signature_sizes, num_docs, page_size=0, term_size=31, canonicalize=1,
-                  num_hashes=1, seed=1, device=-1, shard_rank=0, shard_count=1, hbm_budget=0, shard_mode=0, findere=0):
+                  num_hashes=1, seed=1, device=-1, shard_rank=0, shard_count=1, hbm_budget=0, shard_mode=0,
+                  invalid_bases="error", findere=0):
         """Procedural index generated directly in HBM (benchmark / large parity runs)."""
         lib = _capi.load()
         sigs = (C.c_uint64 * len(signature_sizes))(*[int(s) for s in signature_sizes])
@@ -142,12 +159,13 @@ class Search:
         opts = _options(device, shard_rank, shard_count, hbm_budget, shard_mode)
         check(lib.cobs_gpu_open_synthetic(C.byref(d), C.byref(opts), C.byref(h)))
         s = cls(None, _handle=h)
-        if findere:
-            try:
+        try:
+            if findere:
                 s.set_findere(findere)
-            except Exception:
-                s.close()
-                raise
+            s.invalid_bases = invalid_bases
+        except Exception:
+            s.close()
+            raise
         return s
 
     def close(self):
@@ -229,6 +247,25 @@ class Search:
 
     def _get_findere_call(self, zp):
         return self._lib.cobs_gpu_get_findere(self._h, zp)
+
+    @property
+    def invalid_bases(self):
+        """what a character outside ACGT in a query does: "error" (the call fails, as `cobs query` does), "miss" (a k-mer
+        that holds one is absent from every document) or "skip" (... and leaves the threshold's denominator too); see
+        cobs_gpu_set_invalid_bases"""
+        m = C.c_uint32()
+        check(self._get_invalid_bases_call(C.byref(m)))
+        return INVALID_BASES[m.value]
+
+    @invalid_bases.setter
+    def invalid_bases(self, mode):
+        check(self._set_invalid_bases_call(_invalid_bases_mode(mode)))
+
+    def _set_invalid_bases_call(self, mode):
+        return self._lib.cobs_gpu_set_invalid_bases(self._h, mode)
+
+    def _get_invalid_bases_call(self, mp):
+        return self._lib.cobs_gpu_get_invalid_bases(self._h, mp)
 
     def read_rows(self, file_no, page, row0, nrows, out=None):
         """bulk D2H of whole rows of one held sub-index -> uint8 [nrows, held row bytes]"""
@@ -593,7 +630,7 @@ class MultiSearch(Search):
     device and the exchange over RCCL; search / search_batch / search_arrays / search_packed
     return exactly what Search returns on one GPU."""
 
-    def __init__(self, path, devices, hbm_budget=0, shard_mode=0, findere=0):
+    def __init__(self, path, devices, hbm_budget=0, shard_mode=0, findere=0, invalid_bases="error"):
         self._lib = _capi.load()
         self._m = C.c_void_p()
         self._h = C.c_void_p()
@@ -604,12 +641,13 @@ class MultiSearch(Search):
         check(self._lib.cobs_gpu_multi_open(arr, len(paths), devs, len(devices), C.byref(opts), C.byref(self._m)))
         # rank 0's shard handle answers the geometry / name calls of the base class (not owned)
         self._h = C.c_void_p(self._lib.cobs_gpu_multi_index(self._m, 0))
-        if findere:
-            try:
+        try:
+            if findere:
                 self.set_findere(findere)
-            except Exception:
-                self.close()
-                raise
+            self.invalid_bases = invalid_bases
+        except Exception:
+            self.close()
+            raise
 
     def close(self):
         if getattr(self, "_m", None):
@@ -641,6 +679,12 @@ class MultiSearch(Search):
 
     def _get_findere_call(self, zp):
         return self._lib.cobs_gpu_multi_get_findere(self._m, zp)
+
+    def _set_invalid_bases_call(self, mode):
+        return self._lib.cobs_gpu_multi_set_invalid_bases(self._m, mode)
+
+    def _get_invalid_bases_call(self, mp):
+        return self._lib.cobs_gpu_multi_get_invalid_bases(self._m, mp)
 
     def counts(self, query):
         raise NotImplementedError("raw counts are per shard: use shard(rank).counts(query)")
@@ -705,6 +749,13 @@ class Batch:
     def sync(self, stream=0):
         bad = C.c_size_t(0)
         check(self._lib.cobs_gpu_batch_sync(self._h, C.c_void_p(stream), C.byref(bad)))
+
+    def scored_positions(self, file_no=0):
+        """positions every query was scored over in one file (after sync): the valid ones under invalid_bases "miss" and
+        "skip", len - k + 1 - findere under "error" -- what a score is divided by"""
+        out = np.zeros(max(self.nq, 1), dtype=np.uint32)
+        check(self._lib.cobs_gpu_batch_scored_positions(self._h, file_no, out.ctypes.data))
+        return out[:self.nq]
 
     def counts_device(self):
         """-> (device pointer, element bytes, row stride bytes)"""

@@ -3,7 +3,7 @@
  * (include/cobs_gpu.h): device-resident query batches (inputs and counts stay in HBM: the benchmark's step, the
  * building blocks of the search calls), the one exchange step of the sub-index-sharded multi-GPU layout over RCCL
  * (one rank per process), cobs_gpu_search_batch over such a sharded index, the procedural benchmark index, and findere
- * scoring (a query-time option beyond the reference's search).
+ * scoring and the invalid-bases policy (query-time options beyond the reference's search).
  * Same conventions as cobs_gpu.h: plain pointers and sizes, cobs_gpu_status, nothing aborts.
  */
 #ifndef COBS_GPU_BATCH_H
@@ -47,6 +47,29 @@ cobs_gpu_status cobs_gpu_get_findere(const cobs_gpu_index* ix, uint32_t* z);
 /* findere on every shard of the device list (the same rules as cobs_gpu_set_findere; no shard changes on error) */
 cobs_gpu_status cobs_gpu_multi_set_findere(cobs_gpu_multi* m, uint32_t z);
 cobs_gpu_status cobs_gpu_multi_get_findere(const cobs_gpu_multi* m, uint32_t* z);
+
+/* ---- invalid bases ------------------------------------------------------ */
+/* What a character outside ACGT in a query does (files with canonicalize != 0; the others accept every byte), beyond the
+ * reference, which dies on the first one (classic_search.cpp:93-96).  A scored position p of a query (p < T - z) is VALID
+ * when its k + z characters [p, p + k + z) are all upper-case A C G T; V = a query's valid positions in a file.
+ *   ERROR (0, default): the whole call fails with COBS_GPU_ERR_INVALID_BASE, *bad_query = the first such query.
+ *   MISS  (1): a term that holds such a character is absent from every document and nothing fails: a score counts the
+ *              valid positions whose z + 1 terms are present; thresholds stay ceil(threshold * (T - z)).
+ *   SKIP  (2): the same scores, and invalid positions leave the denominator: the threshold is ceil(threshold * V), at least
+ *              1 when threshold > 0 (a read without a valid position matches nothing), 0 when threshold <= 0.
+ * Score widths and the "single hash in total: index order" rule keep the nominal (T - z) * num_hashes; a query shorter
+ * than k + z still fails the call.  cobs_gpu_hit_positions follows: the bit of an invalid position is 0.  Every call and
+ * batch of the handle uses the policy set when it runs; ranks of a one-rank-per-process sharded search must set the same
+ * one (as with findere).  ERR_ARG: NULL or a mode > 2. */
+enum { COBS_GPU_INVALID_ERROR = 0, COBS_GPU_INVALID_MISS = 1, COBS_GPU_INVALID_SKIP = 2 };
+cobs_gpu_status cobs_gpu_set_invalid_bases(cobs_gpu_index* ix, uint32_t mode);
+cobs_gpu_status cobs_gpu_get_invalid_bases(const cobs_gpu_index* ix, uint32_t* mode);
+/* ... on every shard of the device list (no shard changes on error) */
+cobs_gpu_status cobs_gpu_multi_set_invalid_bases(cobs_gpu_multi* m, uint32_t mode);
+cobs_gpu_status cobs_gpu_multi_get_invalid_bases(const cobs_gpu_multi* m, uint32_t* mode);
+/* The positions every query of a synced batch was scored over in file `file` (out: nq entries): V under MISS and SKIP,
+ * T - z under ERROR (and for a file with canonicalize == 0) -- what a caller divides a score by. */
+cobs_gpu_status cobs_gpu_batch_scored_positions(const cobs_gpu_batch* b, size_t file, uint32_t* out);
 
 /* ---- procedural index ---------------------------------------------------- */
 cobs_gpu_status cobs_gpu_open_synthetic(const cobs_gpu_synth* desc,

@@ -333,6 +333,16 @@ public:
         return z;
     }
 
+    //! what a character outside ACGT in a query does (beyond the reference, which dies): COBS_GPU_INVALID_ERROR (the
+    //! default), _MISS (its k-mers are absent from every document) or _SKIP (... and leave the threshold's denominator);
+    //! cobs_gpu_set_invalid_bases
+    void set_invalid_bases(unsigned mode) { check(cobs_gpu_set_invalid_bases(ix_, mode)); }
+    unsigned invalid_bases() const {
+        uint32_t m = 0;
+        check(cobs_gpu_get_invalid_bases(ix_, &m));
+        return m;
+    }
+
 private:
     static void check(cobs_gpu_status st) {
         if (st != COBS_GPU_OK) throw Error(st, cobs_gpu_last_error());
@@ -424,6 +434,13 @@ public:
         uint32_t z = 0;
         check(cobs_gpu_multi_get_findere(m_, &z));
         return z;
+    }
+    //! the invalid-bases policy on every shard (see ClassicSearch::set_invalid_bases)
+    void set_invalid_bases(unsigned mode) { check(cobs_gpu_multi_set_invalid_bases(m_, mode)); }
+    unsigned invalid_bases() const {
+        uint32_t m = 0;
+        check(cobs_gpu_multi_get_invalid_bases(m_, &m));
+        return m;
     }
 
 private:
