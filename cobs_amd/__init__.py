@@ -11,10 +11,10 @@ from .construct import (ClassicIndexParameters, CompactIndexParameters, Document
                         compact_construct_list, disable_cache, write_synthetic, build_search,
                         classic_combine, compact_combine, classic_construct_random, DocumentEntry, FileType)
 from .querygen import QueryRecord, generate_queries  # noqa: F401
-from .search import Batch, MultiSearch, Search, SearchResult, ShardedBatch, unpack_positions  # noqa: F401
+from .search import Batch, GroupResult, MultiSearch, Search, SearchResult, ShardedBatch, unpack_positions  # noqa: F401
 
 __version__ = "0.2.0"
-__all__ = ["Search", "MultiSearch", "SearchResult", "Batch", "ShardedBatch", "CobsGpuError", "DocumentList", "DocumentEntry", "FileType",
+__all__ = ["Search", "MultiSearch", "SearchResult", "GroupResult", "Batch", "ShardedBatch", "CobsGpuError", "DocumentList", "DocumentEntry", "FileType",
            "ClassicIndexParameters",
            "CompactIndexParameters", "classic_construct", "classic_construct_list", "compact_construct",
            "compact_construct_list", "disable_cache", "write_synthetic", "build_search", "classic_combine", "compact_combine",

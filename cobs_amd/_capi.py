@@ -46,6 +46,10 @@ class Hit(C.Structure):
     _fields_ = [("file_no", C.c_uint32), ("doc", C.c_uint32), ("score", C.c_uint32)]
 
 
+class GroupHit(C.Structure):
+    _fields_ = [("file_no", C.c_uint32), ("doc", C.c_uint32), ("score", C.c_uint32), ("votes", C.c_uint32)]
+
+
 class BuildParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("term_size", C.c_uint32), ("canonicalize", C.c_uint32),
                 ("num_hashes", C.c_uint32), ("false_positive_rate", C.c_double),
@@ -158,6 +162,9 @@ SYMBOLS = {
     "cobs_gpu_hit_positions": (_int, [_vp, C.POINTER(_cp), C.POINTER(_sz), _sz, C.POINTER(Hit), C.POINTER(_sz),
                                       _pu64, _sz, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz)]),
     "cobs_gpu_positions_ms": (_int, [_vp, C.POINTER(C.c_double * 3)]),
+    "cobs_gpu_search_groups": (_int, [_vp, C.POINTER(_cp), C.POINTER(_sz), _sz, C.POINTER(_sz), _sz, _dbl, _dbl, _sz,
+                                      C.POINTER(GroupHit), _sz, C.POINTER(_sz), _pu64, C.POINTER(_sz)]),
+    "cobs_gpu_groups_ms": (_int, [_vp, C.POINTER(C.c_double * 3)]),
     "cobs_gpu_batch_create": (_int, [_vp, _sz, _sz, C.POINTER(_vp)]),
     "cobs_gpu_batch_destroy": (None, [_vp]),
     "cobs_gpu_batch_set_queries": (_int, [_vp, C.POINTER(_cp), C.POINTER(_sz), _sz]),

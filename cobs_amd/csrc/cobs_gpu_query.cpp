@@ -30,6 +30,11 @@ static void usage() {
     std::fprintf(stderr,
                  "usage: cobs_gpu_query -i INDEX [-i INDEX ...] [-t THRESHOLD] [-l LIMIT] "
                  "[-d DEVICE[,DEVICE...]] [--hbm-budget GIB] [--findere Z] [--invalid-bases MODE] [--positions] (QUERY | -f QUERY_FILE)\n"
+                 "       [--group N|all] [--read-threshold X]\n"
+                 "       --group N: every N consecutive records of the query file are one group (all: the whole file); per group\n"
+                 "        one line *<name of its first record><TAB><hits>, then doc_name<TAB>sum<TAB>votes for the documents whose\n"
+                 "        summed score reaches -t of the group's positions; votes = the group's records that reach\n"
+                 "        --read-threshold X (default 0) in the document; not with several devices or --hbm-budget\n"
                  "       --positions: every result line gets a tab and one character per position of the query in that\n"
                  "        document, position 0 first: 1 = the k-mer there (with --findere Z: all Z + 1 from there) is present;\n"
                  "        the number of 1s is the score.  Not with several devices or --hbm-budget.\n"
@@ -205,6 +210,8 @@ int main(int argc, char** argv) {
     int findere = -1;                        // --findere Z; -1: not given (the handle's default, 0)
     unsigned invalid_bases = COBS_GPU_INVALID_ERROR;   // --invalid-bases MODE
     bool positions = false;                  // --positions
+    std::string group;                       // --group N|all
+    double read_threshold = 0.0;             // --read-threshold X
     unsigned num_kmers = 1000, num_queries = 10000, num_warmup = 100;
     size_t seed = std::random_device{}();
     for (int i = 1; i < argc; ++i) {
@@ -260,6 +267,8 @@ int main(int argc, char** argv) {
             else { std::fprintf(stderr, "--invalid-bases: error, miss or skip\n"); return 1; }
         }
         else if (a == "--positions") positions = true;
+        else if (a == "--group") group = need("--group");
+        else if (a == "--read-threshold") read_threshold = std::atof(need("--read-threshold"));
         else if (a == "-h" || a == "--help") { usage(); return 0; }
         else if (!a.empty() && a[0] == '-') { std::fprintf(stderr, "unknown flag %s\n", a.c_str()); usage(); return 1; }
         else if (fpr_mode && index_paths.empty()) index_paths.push_back(a);
@@ -270,6 +279,18 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "--positions: not with several devices (-d A,B / --sharded) or --hbm-budget: "
                              "the rows of a document have to be resident on one GPU\n");
         return 1;
+    }
+    size_t group_size = 0;                   // 0 with --group all
+    if (!group.empty()) {
+        char* end = nullptr;
+        const unsigned long long n = std::strtoull(group.c_str(), &end, 10);
+        if (group != "all" && (*end != '\0' || n == 0)) { std::fprintf(stderr, "--group: a number of records > 0, or all\n"); return 1; }
+        group_size = group == "all" ? 0 : (size_t)n;
+        if (devices.size() > 1 || force_sharded || hbm_budget != 0 || positions || query_file.empty()) {
+            std::fprintf(stderr, "--group: needs a query file (-f); not with several devices (-d A,B / --sharded), --hbm-budget "
+                                 "or --positions\n");
+            return 1;
+        }
     }
     auto open_index = [&]() -> std::unique_ptr<cobs_gpu::BatchSearch> {
         // stdout carries the results in `cobs query` format and nothing else: RCCL prints a
@@ -375,6 +396,20 @@ int main(int argc, char** argv) {
             }
         }
         if (!query.empty()) { queries.push_back(query); comments.push_back(comment); }
+        if (!group.empty()) {
+            std::vector<size_t> offs{0};
+            const size_t step = group_size ? group_size : std::max<size_t>(queries.size(), 1);
+            for (size_t q = 0; q < queries.size(); q += step) offs.push_back(std::min(q + step, queries.size()));
+            std::vector<std::vector<cobs_gpu::ClassicSearch::GroupResult>> results;
+            dynamic_cast<cobs_gpu::ClassicSearch&>(s).search_groups(queries, offs, results, threshold, read_threshold, num_results);
+            for (size_t g = 0; g + 1 < offs.size(); ++g) {
+                std::cout << comments[offs[g]] << '\t' << results[g].size() << '\n';
+                for (const auto& r : results[g]) std::cout << r.doc_name << '\t' << r.score << '\t' << r.votes << '\n';
+            }
+            std::cout.flush();
+            print_timer(s);
+            return 0;
+        }
         if (positions) {
             print_with_positions(dynamic_cast<cobs_gpu::ClassicSearch&>(s), queries, &comments, threshold, num_results);
             std::cout.flush();

@@ -156,6 +156,7 @@ cobs_gpu_batch::~cobs_gpu_batch() {
 
 cobs_gpu_index::~cobs_gpu_index() {
     if (positions) destroy_positions_work(positions);
+    if (groups) destroy_groups_work(groups);
     for (auto* b : scratch) delete b;
     if (xchg_stream) (void)hipStreamDestroy(xchg_stream);
 }

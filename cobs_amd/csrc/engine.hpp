@@ -263,6 +263,7 @@ struct ResultArena {
 struct Exchange;     // comm.cpp: buffers of the RCCL exchange bound to a batch
 struct RankWork;     // rank.cpp: buffers of the on-device ranking of whole score rows
 struct PositionsWork;   // positions.cpp: buffers of cobs_gpu_hit_positions
+struct GroupsWork;      // groups.cpp: scratch batches, accumulators and pool of cobs_gpu_search_groups
 
 }  // namespace cobs_amd
 
@@ -285,6 +286,7 @@ struct cobs_gpu_index {
     cobs_gpu_batch* scratch[kScratch] = {nullptr, nullptr, nullptr};   // workspaces of the host-buffer search API
     hipStream_t xchg_stream = nullptr;   // sharded search: the stream the ranks' agreements and exchanges of its passes run on (sharded.cpp)
     cobs_amd::PositionsWork* positions = nullptr;   // positions.cpp
+    cobs_amd::GroupsWork* groups = nullptr;         // groups.cpp
     ~cobs_gpu_index();
 };
 
@@ -479,6 +481,7 @@ void destroy_exchange(Exchange* x);       // comm.cpp
 // rank.cpp: counts_to_result over the score rows of the last run, on the device
 void destroy_rank_work(RankWork* w);
 void destroy_positions_work(PositionsWork* w);     // positions.cpp
+void destroy_groups_work(GroupsWork* w);           // groups.cpp
 bool rank_on_device_applies(const cobs_gpu_batch* b, size_t nq);
 cobs_gpu_status rank_launch(cobs_gpu_batch* b, size_t q_first, size_t nq, size_t limit);
 void rank_cancel(cobs_gpu_batch* b);

@@ -17,7 +17,7 @@ import sys
 import numpy as np
 
 from . import _capi
-from ._capi import CobsGpuError, Hit, IndexInfo, Options, Synth, check
+from ._capi import CobsGpuError, GroupHit, Hit, IndexInfo, Options, Synth, check
 
 
 class SearchResult:
@@ -34,6 +34,24 @@ class SearchResult:
     def __eq__(self, other):
         return (isinstance(other, SearchResult) and self.doc_name == other.doc_name
                 and self.score == other.score)
+
+
+class GroupResult:
+    """one document of a group's result (Search.search_groups): the sum of the scores of the group's queries in it and the
+    number of those queries it was a hit of at read_threshold"""
+    __slots__ = ("doc_name", "score", "votes")
+
+    def __init__(self, doc_name="", score=0, votes=0):
+        self.doc_name = doc_name
+        self.score = score
+        self.votes = votes
+
+    def __repr__(self):
+        return "GroupResult(doc_name=%r, score=%d, votes=%d)" % (self.doc_name, self.score, self.votes)
+
+    def __eq__(self, other):
+        return (isinstance(other, GroupResult) and self.doc_name == other.doc_name and self.score == other.score
+                and self.votes == other.votes)
 
 
 class ResultList(collections.abc.Sequence):
@@ -576,6 +594,71 @@ class Search:
                         unpack_positions(bits[int(bit_offsets[i]):int(bit_offsets[i + 1])], n)))
         return out
 
+    # -- grouped search: which documents a SET of queries comes from -----------------
+    GROUP_HIT_DTYPE = np.dtype([("file_no", "<u4"), ("doc", "<u4"), ("score", "<u4"), ("votes", "<u4")])
+
+    def search_groups_arrays(self, queries, group_offsets, threshold=0.0, read_threshold=0.0, num_results=0):
+        """cobs_gpu_search_groups: group g is queries[group_offsets[g]:group_offsets[g + 1]] (contiguous; n_groups + 1
+        non-decreasing offsets from 0 to len(queries))
+        -> (hit_offsets uint64 [n_groups + 1], hits GROUP_HIT_DTYPE, positions uint64 [n_groups, num_files]): the records of
+        group g are hits[hit_offsets[g]:hit_offsets[g + 1]], by score (the sum over the group's queries) descending, then
+        (file_no, doc); votes = the group's queries the document was a hit of at read_threshold."""
+        if type(self)._search_batch_call is not Search._search_batch_call:
+            raise CobsGpuError(_capi.ERR_UNSUPPORTED, "groups: not on a device-list handle (a group's totals are per shard)")
+        qs = [q if type(q) is bytes else _as_bytes(q) for q in queries]
+        nq = len(qs)
+        goffs = np.ascontiguousarray(group_offsets, dtype=np.uint64)
+        if goffs.ndim != 1 or len(goffs) < 1:
+            raise ValueError("group_offsets needs n_groups + 1 entries")
+        ng = len(goffs) - 1
+        arr = (C.c_char_p * max(nq, 1))(*qs)
+        lens = (C.c_size_t * max(nq, 1))(*[len(q) for q in qs])
+        offs = np.zeros(ng + 1, dtype=np.uint64)
+        pos = np.zeros((ng, max(self.num_files, 1)), dtype=np.uint64)
+        bad = C.c_size_t(0)
+        if num_results > 0:
+            cap = ng * min(num_results, self.total_counts)
+        elif threshold <= 0:
+            cap = ng * self.total_counts
+        else:
+            cap = 16 * ng + 1024           # (too small: the call reports the needed size and is made again)
+        cap = max(1, cap)
+        while True:
+            hits = np.zeros(cap, dtype=self.GROUP_HIT_DTYPE)
+            st = self._lib.cobs_gpu_search_groups(
+                self._h, arr, lens, nq, C.cast(goffs.ctypes.data, C.POINTER(C.c_size_t)), ng, float(threshold),
+                float(read_threshold), int(num_results), C.cast(hits.ctypes.data, C.POINTER(GroupHit)), cap,
+                C.cast(offs.ctypes.data, C.POINTER(C.c_size_t)), C.cast(pos.ctypes.data, C.POINTER(C.c_uint64)), C.byref(bad))
+            if st == _capi.ERR_CAPACITY and int(offs[ng]) > cap:
+                cap = int(offs[ng])
+                continue
+            check(st)
+            break
+        return offs, hits[:int(offs[ng])], pos[:, :self.num_files]
+
+    def search_groups(self, queries, group_offsets, threshold=0.0, read_threshold=0.0, num_results=0, return_positions=False):
+        """-> one list per group of GroupResult(doc_name, score, votes); return_positions=True: (that, P uint64
+        [n_groups, num_files]), the positions every group was scored over per file (see cobs_gpu_search_groups)"""
+        offs, hits, pos = self.search_groups_arrays(queries, group_offsets, threshold, read_threshold, num_results)
+        rows = hits.tolist()
+        out = [[GroupResult(self._names(f)[d], s, v) for (f, d, s, v) in rows[int(offs[g]):int(offs[g + 1])]]
+               for g in range(len(offs) - 1)]
+        return (out, pos) if return_positions else out
+
+    def search_paired(self, reads1, reads2, threshold=0.0, read_threshold=0.0, num_results=0, return_positions=False):
+        """groups of two: pair i is (reads1[i], reads2[i])"""
+        if len(reads1) != len(reads2):
+            raise ValueError("reads1 and reads2 differ in length")
+        queries = [r for pair in zip(reads1, reads2) for r in pair]
+        return self.search_groups(queries, np.arange(len(reads1) + 1, dtype=np.uint64) * 2, threshold, read_threshold,
+                                  num_results, return_positions)
+
+    def groups_ms(self):
+        """the last search_groups call: accumulate kernel and select kernel (HIP events), host ordering; milliseconds"""
+        t = (C.c_double * 3)()
+        check(self._lib.cobs_gpu_groups_ms(self._h, C.byref(t)))
+        return {"accumulate_ms": t[0], "select_ms": t[1], "order_ms": t[2]}
+
     def positions_ms(self):
         """kernel times of the hit_positions calls since the previous call of this method (HIP events, summed over passes)"""
         t = (C.c_double * 3)()
@@ -857,7 +940,7 @@ class Batch:
         return {"scan_ms": a.value, "hash_ms": b.value}
 
 
-__all__ = ["Search", "SearchResult", "Batch", "CobsGpuError", "unpack_positions"]
+__all__ = ["Search", "SearchResult", "GroupResult", "Batch", "CobsGpuError", "unpack_positions"]
 
 
 class ShardedBatch:

@@ -1,7 +1,7 @@
 /*
  * include/cobs_gpu_batch.h -- the part of libcobs_gpu.so's C ABI that sits BESIDE the drop-in boundary
  * (include/cobs_gpu.h): device-resident query batches (inputs and counts stay in HBM: the benchmark's step, the
- * building blocks of the search calls), the one exchange step of the sub-index-sharded multi-GPU layout over RCCL
+ * building blocks of the search calls), grouped search (per-group document totals and read votes), the one exchange step of the sub-index-sharded multi-GPU layout over RCCL
  * (one rank per process), cobs_gpu_search_batch over such a sharded index, the procedural benchmark index, and findere
  * scoring and the invalid-bases policy (query-time options beyond the reference's search).
  * Same conventions as cobs_gpu.h: plain pointers and sizes, cobs_gpu_status, nothing aborts.
@@ -122,6 +122,35 @@ cobs_gpu_status cobs_gpu_hit_positions(cobs_gpu_index* ix, const char* const* qu
                                        size_t nq, const cobs_gpu_hit* hits, const size_t* hit_offsets,
                                        uint64_t* bits, size_t cap_words, size_t* bit_offsets,
                                        size_t* words_needed, size_t* bad_query);
+
+/* ---- grouped search ------------------------------------------------------ */
+/* Which documents a SET of queries comes from (a read pair, the reads of an amplicon, a whole sample), beyond the
+ * reference: the nq queries form n_groups CONTIGUOUS groups, group g = the queries [group_offsets[g], group_offsets[g+1])
+ * (n_groups + 1 non-decreasing entries, the first 0, the last nq; empty groups are allowed).  With score(q, f, d) exactly
+ * what cobs_gpu_search_batch scores for query q in document d of file f (the handle's findere z and invalid-bases policy):
+ *   score = the SUM of score(q, f, d) over the group's queries,
+ *   votes = the number of its queries with score(q, f, d) >= thr(q, f), the threshold cobs_gpu_search_batch applies for
+ *           read_threshold (ceil(read_threshold * (T - z)), or the `skip` rule) -- "voted" is "was a hit of that search";
+ *           read_threshold <= 0 gives every document the group's size,
+ *   P[g][f] = the positions the group's queries are scored over in file f, summed: T - z under ERROR and MISS, V under SKIP
+ *           (the denominators of the per-query thresholds); written to positions[g * n_files + f] when positions != NULL.
+ * The result of group g is the real documents (padding slots never count) with score >= max(1, ceil(threshold * P[g][f])),
+ * computed in double -- a group with P = 0 returns nothing --, every real document when threshold <= 0; ordered by score
+ * descending, then (file_no, doc) ascending, cut to the first num_results when num_results > 0.  The reference's
+ * "max_counts <= 1: index order" rule does NOT apply to groups.  hits[hit_offsets[g] .. hit_offsets[g+1]) belong to group g.
+ * Sums are 32-bit: a group whose positions in some file could reach 2^32 fails the call with COBS_GPU_ERR_ARG (the message
+ * names the group).  Sums and votes are additive: split such a sample over several calls and add the parts.
+ * The scores never leave the device: every pass's score rows are added to the groups' totals where they lie.
+ * Errors as cobs_gpu_search_batch reports them (too short, an invalid base under ERROR: *bad_query = the offending query);
+ * COBS_GPU_ERR_CAPACITY when cap is too small -- hit_offsets then holds the needed sizes (hit_offsets[n_groups] the total),
+ * known from the one scan that ran; COBS_GPU_ERR_ARG for malformed offsets; COBS_GPU_ERR_UNSUPPORTED on a handle opened
+ * with an HBM budget or as one shard of several (and, in the mirrors, on the device list). */
+typedef struct cobs_gpu_group_hit { uint32_t file_no, doc, score, votes; } cobs_gpu_group_hit;   /* 16 bytes */
+cobs_gpu_status cobs_gpu_search_groups(cobs_gpu_index* ix, const char* const* queries, const size_t* lens, size_t nq,
+                                       const size_t* group_offsets, size_t n_groups,
+                                       double threshold, double read_threshold, size_t num_results,
+                                       cobs_gpu_group_hit* hits, size_t cap, size_t* hit_offsets /* n_groups + 1 */,
+                                       uint64_t* positions /* optional */, size_t* bad_query);
 
 /* score slots per query held by THIS shard (== cobs_gpu_total_counts when
  * unsharded); device count rows have this many elements */

@@ -79,6 +79,10 @@ cobs_gpu_status cobs_gpu_batch_kernel_ms(cobs_gpu_batch* b, float* scan_ms, floa
  * this function, summed over their passes: out[0] = the presence kernel, out[1] = K1 (hashing), out[2] = passes. */
 cobs_gpu_status cobs_gpu_positions_ms(cobs_gpu_index* ix, double out[3]);
 
+/* Durations (ms) of the LAST cobs_gpu_search_groups call on this handle: out[0] = the accumulate kernel (HIP events, summed
+ * over the call's passes), out[1] = the select kernel (HIP events), out[2] = the host's ordering of the records. */
+cobs_gpu_status cobs_gpu_groups_ms(cobs_gpu_index* ix, double out[3]);
+
 /* Diagnostics of tuning builds (libcobs_gpu_timing.so, `make -C cobs_amd/csrc timing`): s_memtime stamps
  * [work-group slot][wave 0..3][8 phases] of the work-groups sampled from the last scan launch after
  * cobs_gpu_set_tuning(ix, "phase_slots", n).  The production library records nothing (*n_words = 0). */

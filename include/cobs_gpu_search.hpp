@@ -324,6 +324,45 @@ public:
         }
     }
 
+    //! one document of a group's result: the sum of the scores of the group's queries and how many of them it was a hit of
+    struct GroupResult {
+        const char* doc_name;
+        uint32_t score, votes;
+    };
+
+    //! which documents a SET of queries comes from (beyond the reference; cobs_gpu_search_groups): group g is the queries
+    //! [group_offsets[g], group_offsets[g + 1]); results[g] holds the documents whose summed score reaches
+    //! max(1, ceil(threshold * P)), by score descending, then (file, document); votes counts the group's queries that
+    //! reach read_threshold in the document.  positions (optional) receives P, [group][file].
+    void search_groups(const std::vector<std::string>& queries, const std::vector<size_t>& group_offsets,
+                       std::vector<std::vector<GroupResult>>& results, double threshold = 0.0, double read_threshold = 0.0,
+                       size_t num_results = 0, std::vector<std::vector<uint64_t>>* positions = nullptr) {
+        if (group_offsets.empty()) throw Error(COBS_GPU_ERR_ARG, "group_offsets needs n_groups + 1 entries");
+        std::vector<const char*> qp;
+        std::vector<size_t> ql;
+        for (const auto& q : queries) { qp.push_back(q.data()); ql.push_back(q.size()); }
+        const size_t ng = group_offsets.size() - 1, nf = cobs_gpu_num_files(ix_);
+        std::vector<size_t> offs(ng + 1, 0);
+        std::vector<uint64_t> pos(ng * nf + 1, 0);
+        std::vector<cobs_gpu_group_hit> hits(16 * ng + 1024);
+        size_t bad = 0;
+        cobs_gpu_status st;
+        for (;;) {
+            st = cobs_gpu_search_groups(ix_, qp.data(), ql.data(), queries.size(), group_offsets.data(), ng, threshold,
+                                        read_threshold, num_results, hits.data(), hits.size(), offs.data(), pos.data(), &bad);
+            if (st != COBS_GPU_ERR_CAPACITY || offs[ng] <= hits.size()) break;
+            hits.resize(offs[ng]);          // (the call reported the needed size)
+        }
+        check(st);
+        results.assign(ng, {});
+        if (positions) positions->assign(ng, {});
+        for (size_t g = 0; g < ng; ++g) {
+            for (size_t i = offs[g]; i < offs[g + 1]; ++i)
+                results[g].push_back(GroupResult{cobs_gpu_doc_name(ix_, hits[i].file_no, hits[i].doc), hits[i].score, hits[i].votes});
+            if (positions) (*positions)[g].assign(pos.begin() + g * nf, pos.begin() + (g + 1) * nf);
+        }
+    }
+
     //! findere z (0..7, beyond the reference): a position scores only when its z + 1 consecutive terms are all present
     //! (cobs_gpu_set_findere); 0 = the reference's count
     void set_findere(unsigned z) { check(cobs_gpu_set_findere(ix_, z)); }

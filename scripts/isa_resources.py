@@ -18,12 +18,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def main():
     out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "isa_resources.txt")
-    src = os.path.join(ROOT, "cobs_amd", "csrc", "kernels.hip")
-    with tempfile.TemporaryDirectory() as tmp:
-        subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
-                               "-I" + os.path.dirname(src), "--save-temps", "-c", src, "-o", "k.o"], cwd=tmp,
-                              stderr=subprocess.DEVNULL)
-        asm = open(os.path.join(tmp, "kernels-hip-amdgcn-amd-amdhsa-gfx950.s")).read()
+    # the scan kernels, and the grouped-search kernels (group_kernels.hip: accumulate, select, zero)
+    asm = ""
+    for name in ("kernels", "group_kernels"):
+        src = os.path.join(ROOT, "cobs_amd", "csrc", name + ".hip")
+        with tempfile.TemporaryDirectory() as tmp:
+            subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
+                                   "-I" + os.path.dirname(src), "--save-temps", "-c", src, "-o", "k.o"], cwd=tmp,
+                                  stderr=subprocess.DEVNULL)
+            asm += open(os.path.join(tmp, name + "-hip-amdgcn-amd-amdhsa-gfx950.s")).read() + "\n"
     head = subprocess.run(["git", "rev-parse", "--short", "HEAD"], cwd=ROOT, capture_output=True, text=True).stdout.strip()
     rows = []
     for m in re.finditer(r"- \.agpr_count:.*?(?=\n  - \.agpr_count:|\namdhsa\.target)", asm, re.S):
@@ -34,7 +37,7 @@ def main():
             return r.group(1) if r else "?"
         sym = g("name")
         dem = subprocess.run(["c++filt", sym], capture_output=True, text=True).stdout.strip()
-        dem = dem.replace("cobs_amd::", "").replace("unsigned char", "u8").replace("unsigned short", "u16") \
+        dem = dem.replace("cobs_amd::", "").replace("(anonymous namespace)::", "").replace("unsigned char", "u8").replace("unsigned short", "u16") \
                  .replace("unsigned int", "u32").replace("unsigned long", "u64")
         dem = re.sub(r"\(.*\)$", "", dem).replace("void ", "")
         vg, ag = int(g("vgpr_count")), int(g("agpr_count"))
@@ -44,7 +47,7 @@ def main():
         rows.append((dem, vg, ag, int(g("sgpr_count")), int(g("group_segment_fixed_size")),
                      int(g("private_segment_fixed_size")), g("vgpr_spill_count"), waves))
     rows.sort()
-    lines = ["# kernels.hip @ %s, hipcc -O3 --offload-arch=gfx950; from the code object metadata (.s of --save-temps)" % head,
+    lines = ["# kernels.hip, group_kernels.hip @ %s, hipcc -O3 --offload-arch=gfx950; from the code object metadata (.s of --save-temps)" % head,
              "# static_lds excludes the dynamic LDS a launch adds (scan_kernel: merge buffers + expansion table)",
              "%-64s %5s %5s %5s %10s %8s %6s %10s" % ("kernel", "vgpr", "agpr", "sgpr", "static_lds", "scratch", "spill",
                                                      "waves/SIMD")]
