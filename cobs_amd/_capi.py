@@ -165,6 +165,9 @@ SYMBOLS = {
     "cobs_gpu_search_groups": (_int, [_vp, C.POINTER(_cp), C.POINTER(_sz), _sz, C.POINTER(_sz), _sz, _dbl, _dbl, _sz,
                                       C.POINTER(GroupHit), _sz, C.POINTER(_sz), _pu64, C.POINTER(_sz)]),
     "cobs_gpu_groups_ms": (_int, [_vp, C.POINTER(C.c_double * 3)]),
+    "cobs_gpu_doc_bits": (_int, [_vp, _sz, C.POINTER(_u64), _sz, C.POINTER(_sz)]),
+    "cobs_gpu_doc_bits_ms": (_int, [_vp, C.POINTER(C.c_double * 4)]),
+    "cobs_gpu_doc_bits_probe_ms": (_int, [_vp, _sz, C.POINTER(C.c_double)]),
     "cobs_gpu_batch_create": (_int, [_vp, _sz, _sz, C.POINTER(_vp)]),
     "cobs_gpu_batch_destroy": (None, [_vp]),
     "cobs_gpu_batch_set_queries": (_int, [_vp, C.POINTER(_cp), C.POINTER(_sz), _sz]),

@@ -15,6 +15,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <chrono>
+#include <cmath>
 #include <fstream>
 #include <iostream>
 #include <memory>
@@ -29,7 +30,11 @@
 static void usage() {
     std::fprintf(stderr,
                  "usage: cobs_gpu_query -i INDEX [-i INDEX ...] [-t THRESHOLD] [-l LIMIT] "
-                 "[-d DEVICE[,DEVICE...]] [--hbm-budget GIB] [--findere Z] [--invalid-bases MODE] [--positions] (QUERY | -f QUERY_FILE)\n"
+                 "[-d DEVICE[,DEVICE...]] [--hbm-budget GIB] [--findere Z] [--invalid-bases MODE] [--positions] [--fpr-adjust] (QUERY | -f QUERY_FILE)\n"
+                 "       cobs_gpu_query doc-stats INDEX [--fill-above X]\n"
+                 "         one line per document: file, name, sub-index, S_p, bits set in its filter, fill = bits / S_p, fpr = fill^H\n"
+                 "       --fpr-adjust: every result line gets expected_fp (the positions the document's fill alone is expected to\n"
+                 "         hit) and adjusted (the estimate of the truly shared positions) appended\n"
                  "       [--group N|all] [--read-threshold X]\n"
                  "       --group N: every N consecutive records of the query file are one group (all: the whole file); per group\n"
                  "        one line *<name of its first record><TAB><hits>, then doc_name<TAB>sum<TAB>votes for the documents whose\n"
@@ -170,18 +175,92 @@ static std::string position_string(const std::vector<uint64_t>& words, size_t n)
 }
 
 // the queries of a `query` call with --positions: the result lines of `cobs query`, each with its 0/1 string appended
+static std::vector<cobs_gpu::ClassicSearch::Adjusted> adjusted_of(cobs_gpu::ClassicSearch& s, const std::string& query,
+                                                                  const std::vector<cobs_gpu::SearchResult>& result);
+static std::string adjusted_columns(const cobs_gpu::ClassicSearch::Adjusted& a);
+
 static void print_with_positions(cobs_gpu::ClassicSearch& s, const std::vector<std::string>& queries,
-                                 const std::vector<std::string>* comments, double threshold, size_t num_results) {
+                                 const std::vector<std::string>* comments, double threshold, size_t num_results, bool fpr_adjust) {
     std::vector<std::vector<cobs_gpu::SearchResult>> results;
     std::vector<std::vector<std::vector<uint64_t>>> pos;
     std::vector<std::vector<size_t>> npos;
     s.search_batch_positions(queries, results, pos, threshold, num_results, &npos);
     for (size_t q = 0; q < queries.size(); ++q) {
         if (comments) std::cout << (*comments)[q] << '\t' << results[q].size() << '\n';
+        std::vector<cobs_gpu::ClassicSearch::Adjusted> adj;
+        if (fpr_adjust) adj = adjusted_of(s, queries[q], results[q]);
         for (size_t i = 0; i < results[q].size(); ++i)
             std::cout << results[q][i].doc_name << '\t' << results[q][i].score << '\t'
-                      << position_string(pos[q][i], npos[q][i]) << '\n';
+                      << position_string(pos[q][i], npos[q][i]) << (fpr_adjust ? adjusted_columns(adj[i]) : std::string()) << '\n';
     }
+}
+
+// --fpr-adjust: "\texpected_fp\tadjusted" of every result of one query.  Under --invalid-bases skip the positions are the
+// query's valid ones per file, read from a device batch of that one query (cobs_gpu_batch_scored_positions).
+static std::vector<cobs_gpu::ClassicSearch::Adjusted> adjusted_of(cobs_gpu::ClassicSearch& s, const std::string& query,
+                                                                  const std::vector<cobs_gpu::SearchResult>& result) {
+    if (s.invalid_bases() != COBS_GPU_INVALID_SKIP) return s.adjust(result, query.size());
+    const size_t nf = cobs_gpu_num_files(s.handle());
+    std::vector<uint64_t> valid(nf, 0);
+    cobs_gpu_batch* b = nullptr;
+    auto check = [&](cobs_gpu_status st) {
+        if (st == COBS_GPU_OK) return;
+        if (b) cobs_gpu_batch_destroy(b);
+        throw cobs_gpu::Error(st, cobs_gpu_last_error());
+    };
+    check(cobs_gpu_batch_create(s.handle(), 1, query.size(), &b));
+    const char* qp = query.data();
+    const size_t ql = query.size();
+    size_t bad = 0;
+    check(cobs_gpu_batch_set_queries(b, &qp, &ql, 1));
+    check(cobs_gpu_batch_run(b, 0.0, nullptr));
+    check(cobs_gpu_batch_sync(b, nullptr, &bad));
+    for (size_t f = 0; f < nf; ++f) {
+        uint32_t v = 0;
+        check(cobs_gpu_batch_scored_positions(b, f, &v));
+        valid[f] = v;
+    }
+    cobs_gpu_batch_destroy(b);
+    return s.adjust(result, query.size(), &valid);
+}
+
+static std::string adjusted_columns(const cobs_gpu::ClassicSearch::Adjusted& a) {
+    char buf[96];
+    std::snprintf(buf, sizeof buf, "\t%.2f\t%.2f", a.expected_fp, a.adjusted);
+    return buf;
+}
+
+// `doc-stats INDEX [--fill-above X]`: file  doc_name  sub_index  S_p  bits  fill  fpr, one line per real document
+static int doc_stats(int argc, char** argv) {
+    std::string path;
+    double above = -1.0;
+    for (int i = 2; i < argc; ++i) {
+        const std::string a = argv[i];
+        if (a == "--fill-above" && i + 1 < argc) above = std::atof(argv[++i]);
+        else if (!a.empty() && a[0] != '-' && path.empty()) path = a;
+        else { usage(); return 1; }
+    }
+    if (path.empty()) { usage(); return 1; }
+    try {
+        cobs_gpu::ClassicSearch s(path);
+        for (size_t f = 0; f < cobs_gpu_num_files(s.handle()); ++f) {
+            cobs_gpu_index_info info;
+            if (cobs_gpu_info(s.handle(), f, &info) != COBS_GPU_OK) throw cobs_gpu::Error(COBS_GPU_ERR_ARG, cobs_gpu_last_error());
+            const std::vector<uint64_t> bits = s.doc_bits(f);
+            const std::vector<double> fill = s.doc_fill(f);
+            for (uint64_t d = 0; d < info.num_docs; ++d) {
+                if (!(fill[d] > above)) continue;
+                const uint32_t page = info.kind == 0 ? 0u : (uint32_t)(d / (8 * info.page_size));
+                std::printf("%zu\t%s\t%u\t%llu\t%llu\t%.6f\t%.6f\n", f, cobs_gpu_doc_name(s.handle(), f, d), page,
+                            (unsigned long long)cobs_gpu_signature_size(s.handle(), f, page), (unsigned long long)bits[d], fill[d],
+                            std::pow(fill[d], (double)info.num_hashes));
+            }
+        }
+    } catch (const cobs_gpu::Error& e) {
+        std::fprintf(stderr, "EXCEPTION: %s\n", e.what());
+        return 1;
+    }
+    return 0;
 }
 
 int cobs_gpu_tools_main(int argc, char** argv);      // cobs_gpu_tools.cpp: *-construct, classic-combine, compact-construct-combine
@@ -191,6 +270,7 @@ int main(int argc, char** argv) {
         const int rc = cobs_gpu_tools_main(argc, argv);
         if (rc >= 0) return rc;
         if (argc > 1 && std::string(argv[1]) == "query") { ++argv; --argc; }       // `cobs query ...`
+        if (argc > 1 && std::string(argv[1]) == "doc-stats") return doc_stats(argc, argv);
     }
     // `cobs benchmark-fpr IN_FILE [-k N] [-q N] [-w N] [-d|--dist] [--seed S]` (src/cobs.cpp:672-730): the index is the
     // positional argument and -d means --dist, as there; the device list of this tool is spelled --device in this mode
@@ -210,6 +290,7 @@ int main(int argc, char** argv) {
     int findere = -1;                        // --findere Z; -1: not given (the handle's default, 0)
     unsigned invalid_bases = COBS_GPU_INVALID_ERROR;   // --invalid-bases MODE
     bool positions = false;                  // --positions
+    bool fpr_adjust = false;                 // --fpr-adjust
     std::string group;                       // --group N|all
     double read_threshold = 0.0;             // --read-threshold X
     unsigned num_kmers = 1000, num_queries = 10000, num_warmup = 100;
@@ -267,6 +348,7 @@ int main(int argc, char** argv) {
             else { std::fprintf(stderr, "--invalid-bases: error, miss or skip\n"); return 1; }
         }
         else if (a == "--positions") positions = true;
+        else if (a == "--fpr-adjust") fpr_adjust = true;
         else if (a == "--group") group = need("--group");
         else if (a == "--read-threshold") read_threshold = std::atof(need("--read-threshold"));
         else if (a == "-h" || a == "--help") { usage(); return 0; }
@@ -281,6 +363,10 @@ int main(int argc, char** argv) {
         return 1;
     }
     size_t group_size = 0;                   // 0 with --group all
+    if (fpr_adjust && (devices.size() > 1 || force_sharded || !group.empty())) {
+        std::fprintf(stderr, "--fpr-adjust: not with several devices (-d A,B / --sharded: a document's filter lives on one rank) or --group\n");
+        return 1;
+    }
     if (!group.empty()) {
         char* end = nullptr;
         const unsigned long long n = std::strtoull(group.c_str(), &end, 10);
@@ -367,7 +453,7 @@ int main(int argc, char** argv) {
         std::unique_ptr<cobs_gpu::BatchSearch> sp = open_index();
         cobs_gpu::BatchSearch& s = *sp;
         if (!query_line.empty() && positions) {
-            print_with_positions(dynamic_cast<cobs_gpu::ClassicSearch&>(s), {query_line}, nullptr, threshold, num_results);
+            print_with_positions(dynamic_cast<cobs_gpu::ClassicSearch&>(s), {query_line}, nullptr, threshold, num_results, fpr_adjust);
             std::cout.flush();
             print_timer(s);
             return 0;
@@ -375,7 +461,10 @@ int main(int argc, char** argv) {
         if (!query_line.empty()) {
             std::vector<cobs_gpu::SearchResult> result;
             s.search(query_line, result, threshold, num_results);
-            for (const auto& r : result) std::cout << r.doc_name << '\t' << r.score << '\n';
+            std::vector<cobs_gpu::ClassicSearch::Adjusted> adj;
+            if (fpr_adjust) adj = adjusted_of(dynamic_cast<cobs_gpu::ClassicSearch&>(s), query_line, result);
+            for (size_t i = 0; i < result.size(); ++i)
+                std::cout << result[i].doc_name << '\t' << result[i].score << (fpr_adjust ? adjusted_columns(adj[i]) : std::string()) << '\n';
             std::cout.flush();
             print_timer(s);
             return 0;
@@ -411,7 +500,7 @@ int main(int argc, char** argv) {
             return 0;
         }
         if (positions) {
-            print_with_positions(dynamic_cast<cobs_gpu::ClassicSearch&>(s), queries, &comments, threshold, num_results);
+            print_with_positions(dynamic_cast<cobs_gpu::ClassicSearch&>(s), queries, &comments, threshold, num_results, fpr_adjust);
             std::cout.flush();
             print_timer(s);
             return 0;
@@ -420,7 +509,11 @@ int main(int argc, char** argv) {
         s.search_batch(queries, results, threshold, num_results);
         for (size_t q = 0; q < queries.size(); ++q) {
             std::cout << comments[q] << '\t' << results[q].size() << '\n';
-            for (const auto& r : results[q]) std::cout << r.doc_name << '\t' << r.score << '\n';
+            std::vector<cobs_gpu::ClassicSearch::Adjusted> adj;
+            if (fpr_adjust) adj = adjusted_of(dynamic_cast<cobs_gpu::ClassicSearch&>(s), queries[q], results[q]);
+            for (size_t i = 0; i < results[q].size(); ++i)
+                std::cout << results[q][i].doc_name << '\t' << results[q][i].score
+                          << (fpr_adjust ? adjusted_columns(adj[i]) : std::string()) << '\n';
         }
         std::cout.flush();
         print_timer(s);

@@ -157,6 +157,7 @@ cobs_gpu_batch::~cobs_gpu_batch() {
 cobs_gpu_index::~cobs_gpu_index() {
     if (positions) destroy_positions_work(positions);
     if (groups) destroy_groups_work(groups);
+    if (fill) destroy_fill_work(fill);
     for (auto* b : scratch) delete b;
     if (xchg_stream) (void)hipStreamDestroy(xchg_stream);
 }
@@ -799,6 +800,7 @@ cobs_gpu_status cobs_gpu_plant(cobs_gpu_index* ix, size_t f, const char* text, s
         a.num_hashes = (uint32_t)p.meta.num_hashes;
         a.ndocs = (uint32_t)ndocs;
         a.bad = d_bad.p;
+        drop_fill_cache(ix, f);          // the file's bits change: cobs_gpu_doc_bits counts again
         HIP_TRY(launch_plant(a, nullptr));
         uint32_t bad = 0;
         HIP_TRY(hipMemcpy(&bad, d_bad.p, 4, hipMemcpyDeviceToHost));

@@ -54,6 +54,39 @@ class GroupResult:
                 and self.votes == other.votes)
 
 
+class AdjustedResult(SearchResult):
+    """a SearchResult that also says what its score is worth (Search.search_adjusted): expected_fp = the positions the
+    document's filter fill alone is expected to hit, adjusted = the estimate of the positions that are truly shared"""
+    __slots__ = ("expected_fp", "adjusted")
+
+    def __init__(self, doc_name="", score=0, expected_fp=0.0, adjusted=0.0):
+        SearchResult.__init__(self, doc_name, score)
+        self.expected_fp = expected_fp
+        self.adjusted = adjusted
+
+    def __repr__(self):
+        return "AdjustedResult(doc_name=%r, score=%d, expected_fp=%.2f, adjusted=%.2f)" % (
+            self.doc_name, self.score, self.expected_fp, self.adjusted)
+
+
+def fpr_adjust(score, positions, bits, sig, num_hashes, z=0):
+    """What a score is worth, from the document's filter fill (host arithmetic in double, no device; scalars or arrays):
+    fill = bits / sig, fpr = fill ** num_hashes (a k-mer unrelated to the document hits it), q = fpr ** (z + 1) (a findere
+    window of z + 1 such k-mers), expected_fp = positions * q, and the method-of-moments estimate of the positions that
+    are truly shared, adjusted = max(0, (score - expected_fp) / (1 - q)), 0 where q >= 1 (a saturated filter says nothing).
+    -> (expected_fp, adjusted) as float64"""
+    s = np.asarray(score, dtype=np.float64)
+    P = np.asarray(positions, dtype=np.float64)
+    fill = np.asarray(bits, dtype=np.float64) / np.asarray(sig, dtype=np.float64)
+    q = np.power(np.power(fill, float(num_hashes)), float(int(z) + 1))
+    expected = P * q
+    sat = q >= 1.0
+    adjusted = np.where(sat, 0.0, np.maximum(0.0, (s - expected) / np.where(sat, 1.0, 1.0 - q)))
+    if adjusted.ndim == 0:
+        return float(expected), float(adjusted)
+    return expected, adjusted
+
+
 class ResultList(collections.abc.Sequence):
     """The result of one query when it is long (the default call returns every document of the index): behaves
     like the reference's list of SearchResult -- len(), indexing, slicing, iteration, equality with a list -- but
@@ -303,6 +336,77 @@ class Search:
         u32p = C.POINTER(C.c_uint32)
         check(self._lib.cobs_gpu_plant(self._h, file_no, text, len(text), docs.ctypes.data_as(u32p),
                                        keep.ctypes.data_as(u32p), len(docs), int(salt)))
+
+    # -- filter fill: what a score is worth ------------------------------------
+    def doc_bits(self, file_no=0):
+        """cobs_gpu_doc_bits: the bits set in every document's Bloom filter -> uint64 [slot_count], one entry per score
+        slot this handle holds of the file (padding slots included; the whole file on an unsharded handle).  Counted on
+        the device on the first request and cached by the library."""
+        need = C.c_size_t(0)
+        st = self._lib.cobs_gpu_doc_bits(self._h, int(file_no), None, 0, C.byref(need))
+        if st != _capi.ERR_CAPACITY:
+            check(st)
+        out = np.zeros(need.value, dtype=np.uint64)
+        check(self._lib.cobs_gpu_doc_bits(self._h, int(file_no), out.ctypes.data_as(C.POINTER(C.c_uint64)), out.size, C.byref(need)))
+        return out
+
+    def _doc_sigs(self, file_no):
+        """signature size S_p of the sub-index of every real document of a file -> uint64 [num_docs]"""
+        i = self.info(file_no)
+        n = int(i.num_docs)
+        if int(i.kind) == 0:
+            return np.full(n, self.signature_size(file_no, 0), dtype=np.uint64)
+        sigs = np.array([self.signature_size(file_no, p) for p in range(int(i.num_pages))], dtype=np.uint64)
+        return sigs[np.arange(n) // (8 * int(i.page_size))]
+
+    def _real_doc_bits(self, file_no):
+        i = self.info(file_no)
+        if int(i.slot_begin) != 0 or int(i.slot_count) < int(i.num_docs):
+            raise CobsGpuError(_capi.ERR_UNSUPPORTED, "this handle holds a shard of the file's documents: use doc_bits")
+        return self.doc_bits(file_no)[:int(i.num_docs)]       # (document d is score slot d; padding slots follow the last)
+
+    def doc_fill(self, file_no=0):
+        """fill ratio of every real document's filter, bits / S_p -> float64 [num_docs]"""
+        return self._real_doc_bits(file_no).astype(np.float64) / self._doc_sigs(file_no).astype(np.float64)
+
+    def doc_fpr(self, file_no=0):
+        """the probability that a k-mer unrelated to a document hits it, fill ** num_hashes -> float64 [num_docs]"""
+        return np.power(self.doc_fill(file_no), float(int(self.info(file_no).num_hashes)))
+
+    def doc_bits_ms(self):
+        """the doc_bits sweeps of this handle so far: kernel ms, index bytes read, PCIe copy ms, sweeps"""
+        t = (C.c_double * 4)()
+        check(self._lib.cobs_gpu_doc_bits_ms(self._h, C.byref(t)))
+        return {"kernel_ms": t[0], "bytes_read": int(t[1]), "pcie_ms": t[2], "passes": int(t[3])}
+
+    def search_adjusted(self, query, threshold=0.0, num_results=0):
+        """search() whose results also carry expected_fp and adjusted (fpr_adjust over the document's fill, the handle's
+        findere z and the positions the search scored: T - z, or the valid positions V under invalid_bases "skip").
+        -> list of AdjustedResult in search()'s order.  [search() itself keeps the reference's signature.]"""
+        q = _as_bytes(query)
+        hits = self.search_hits([q], threshold, num_results)[0]
+        z = self.findere
+        valid = None
+        if self.invalid_bases == "skip":
+            b = Batch(self)
+            try:
+                b.set_queries([q])
+                b.run(0.0)
+                b.sync()
+                valid = [int(b.scored_positions(f)[0]) for f in range(self.num_files)]
+            finally:
+                b.close()
+        per_file = {}
+        out = []
+        for f, d, s in hits:
+            if f not in per_file:
+                i = self.info(f)
+                P = valid[f] if valid is not None else len(q) - int(i.term_size) + 1 - z
+                per_file[f] = (self._real_doc_bits(f), self._doc_sigs(f), int(i.num_hashes), P)
+            bits, sigs, H, P = per_file[f]
+            e, a = fpr_adjust(s, P, int(bits[d]), int(sigs[d]), H, z)
+            out.append(AdjustedResult(self._names(f)[d], s, e, a))
+        return out
 
     # -- queries -------------------------------------------------------------
     def search(self, query, threshold=0.0, num_results=0):
@@ -772,6 +876,10 @@ class MultiSearch(Search):
     def counts(self, query):
         raise NotImplementedError("raw counts are per shard: use shard(rank).counts(query)")
 
+    def doc_bits(self, file_no=0):
+        """refused: a document's filter lives on one rank (doc_fill, doc_fpr and search_adjusted follow)"""
+        raise CobsGpuError(_capi.ERR_UNSUPPORTED, "doc_bits: not on a device-list handle (ask the shards: shard(rank).doc_bits)")
+
 
 class _DevArray:
     """__cuda_array_interface__ view of HBM owned by libcobs_gpu (zero copy into torch)."""
@@ -940,7 +1048,7 @@ class Batch:
         return {"scan_ms": a.value, "hash_ms": b.value}
 
 
-__all__ = ["Search", "SearchResult", "GroupResult", "Batch", "CobsGpuError", "unpack_positions"]
+__all__ = ["Search", "SearchResult", "GroupResult", "AdjustedResult", "Batch", "CobsGpuError", "unpack_positions", "fpr_adjust"]
 
 
 class ShardedBatch:

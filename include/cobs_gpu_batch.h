@@ -152,6 +152,21 @@ cobs_gpu_status cobs_gpu_search_groups(cobs_gpu_index* ix, const char* const* qu
                                        cobs_gpu_group_hit* hits, size_t cap, size_t* hit_offsets /* n_groups + 1 */,
                                        uint64_t* positions /* optional */, size_t* bad_query);
 
+/* ---- filter fill --------------------------------------------------------- */
+/* How many bits every document's Bloom filter has set, beyond the reference: bits[i] = the rows r in [0, S_p) of the
+ * document's sub-index whose bit of score slot slot_begin + i is set (the zero row the engine appends is never counted;
+ * a padding slot is counted like any other column and is 0 in a well-formed file).  `bits` receives slot_count entries
+ * for the file-level slots [slot_begin, slot_begin + slot_count) of cobs_gpu_index_info -- the file's counts_size on an
+ * unsharded handle; *needed (optional) is always set to that number.  With fill = bits / S_p a k-mer unrelated to the
+ * document still hits it with probability fill^H: what a raw score is worth (the mirrors' doc_fill / fpr_adjust).
+ * Counted on the device in one sweep over the index -- resident chunks where they lie, the streamed chunks of a handle
+ * with an HBM budget whole through its stream buffers, once each -- on the first request for a file and cached on the
+ * handle (8 bytes per slot); cobs_gpu_plant drops the cache of the file it changes.
+ * COBS_GPU_ERR_ARG: NULL handle or file_no out of range (before any device work); COBS_GPU_ERR_CAPACITY: cap is too
+ * small (host arithmetic, nothing runs; bits may be NULL when cap is 0).  The device list (cobs_gpu_multi_*) has no
+ * counterpart: ask the shards (cobs_gpu_multi_index). */
+cobs_gpu_status cobs_gpu_doc_bits(cobs_gpu_index* ix, size_t file_no, uint64_t* bits, size_t cap, size_t* needed);
+
 /* score slots per query held by THIS shard (== cobs_gpu_total_counts when
  * unsharded); device count rows have this many elements */
 uint64_t cobs_gpu_local_counts(const cobs_gpu_index* ix);

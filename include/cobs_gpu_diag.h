@@ -83,6 +83,16 @@ cobs_gpu_status cobs_gpu_positions_ms(cobs_gpu_index* ix, double out[3]);
  * over the call's passes), out[1] = the select kernel (HIP events), out[2] = the host's ordering of the records. */
 cobs_gpu_status cobs_gpu_groups_ms(cobs_gpu_index* ix, double out[3]);
 
+/* The cobs_gpu_doc_bits sweeps of this handle so far (cache hits add nothing): out[0] = milliseconds of the counting
+ * kernels (HIP events), out[1] = index bytes they read (rows x valid row bytes), out[2] = milliseconds between HIP events
+ * recorded on the copy stream before and after every streamed chunk is brought in (0 on a resident handle) -- the copies
+ * over PCIe and, for a file whose mapping is not registered with HIP, the host threads that pack the rows into pinned
+ * staging before each copy is queued --, out[3] = sweeps (one per file counted). */
+cobs_gpu_status cobs_gpu_doc_bits_ms(cobs_gpu_index* ix, double out[4]);
+/* The arithmetic-free yardstick of the counting kernel: the same loads over the resident chunks of file_no, one XOR per
+ * load and one store per lane; *ms = HIP-event milliseconds of one such sweep (scripts/probes/fill_probe.py). */
+cobs_gpu_status cobs_gpu_doc_bits_probe_ms(cobs_gpu_index* ix, size_t file_no, double* ms);
+
 /* Diagnostics of tuning builds (libcobs_gpu_timing.so, `make -C cobs_amd/csrc timing`): s_memtime stamps
  * [work-group slot][wave 0..3][8 phases] of the work-groups sampled from the last scan launch after
  * cobs_gpu_set_tuning(ix, "phase_slots", n).  The production library records nothing (*n_words = 0). */

@@ -20,6 +20,7 @@
 #pragma once
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -27,6 +28,8 @@
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <unordered_map>
+#include <utility>
 #include <vector>
 
 #include "cobs_gpu.h"
@@ -363,6 +366,72 @@ public:
         }
     }
 
+    //! the bits set in every document's Bloom filter (beyond the reference; cobs_gpu_doc_bits): one entry per score slot
+    //! this handle holds of the file, counted on the device on the first request and cached by the library
+    std::vector<uint64_t> doc_bits(size_t file_no = 0) {
+        size_t need = 0;
+        const cobs_gpu_status st = cobs_gpu_doc_bits(ix_, file_no, nullptr, 0, &need);
+        if (st != COBS_GPU_ERR_CAPACITY) check(st);
+        std::vector<uint64_t> bits(need);
+        check(cobs_gpu_doc_bits(ix_, file_no, bits.data(), bits.size(), &need));
+        return bits;
+    }
+
+    //! fill ratio bits / S_p of every REAL document of a file (an unsharded handle: document d is score slot d)
+    std::vector<double> doc_fill(size_t file_no = 0) {
+        const std::vector<uint64_t> bits = doc_bits(file_no);
+        const cobs_gpu_index_info info = whole_file_info(file_no);
+        std::vector<double> fill(info.num_docs);
+        for (uint64_t d = 0; d < info.num_docs; ++d)
+            fill[d] = (double)bits[d] / (double)cobs_gpu_signature_size(ix_, file_no, page_of(info, d));
+        return fill;
+    }
+
+    //! what a score is worth: expected_fp = the positions the document's filter fill alone is expected to hit, adjusted =
+    //! the method-of-moments estimate of the positions that are truly shared (cobs_gpu_batch.h, "filter fill")
+    struct Adjusted {
+        double expected_fp = 0, adjusted = 0;
+    };
+    static Adjusted fpr_adjust(double score, double positions, uint64_t bits, uint64_t sig, uint64_t num_hashes, unsigned z = 0) {
+        const double fill = (double)bits / (double)sig;
+        const double q = std::pow(std::pow(fill, (double)num_hashes), (double)(z + 1));
+        Adjusted a;
+        a.expected_fp = positions * q;
+        a.adjusted = q >= 1.0 ? 0.0 : std::max(0.0, (score - a.expected_fp) / (1.0 - q));
+        return a;
+    }
+
+    //! ... for the results of a search of a query of query_length characters on this object (result[i].doc_name as the
+    //! search returned it: the name's address identifies the document).  The positions are T - z; under
+    //! COBS_GPU_INVALID_SKIP they are the query's valid positions, which this call does not have at hand: pass them per
+    //! file (cobs_gpu_batch_scored_positions) or it throws.
+    std::vector<Adjusted> adjust(const std::vector<SearchResult>& result, size_t query_length,
+                                 const std::vector<uint64_t>* positions_per_file = nullptr) {
+        const size_t nf = cobs_gpu_num_files(ix_);
+        if (invalid_bases() == COBS_GPU_INVALID_SKIP && !(positions_per_file && positions_per_file->size() == nf))
+            throw Error(COBS_GPU_ERR_UNSUPPORTED, "adjust: under invalid_bases = skip the valid positions per file are needed");
+        const unsigned z = findere();
+        std::vector<cobs_gpu_index_info> info(nf);
+        std::vector<std::vector<uint64_t>> bits(nf);
+        for (size_t f = 0; f < nf; ++f) info[f] = whole_file_info(f);
+        if (doc_of_name_.empty())
+            for (size_t f = 0; f < nf; ++f)
+                for (uint64_t d = 0; d < info[f].num_docs; ++d) doc_of_name_[cobs_gpu_doc_name(ix_, f, d)] = {f, d};
+        std::vector<Adjusted> out(result.size());
+        for (size_t i = 0; i < result.size(); ++i) {
+            const auto it = doc_of_name_.find(result[i].doc_name);
+            if (it == doc_of_name_.end()) throw Error(COBS_GPU_ERR_ARG, "adjust: a result that is not from this object");
+            const size_t f = it->second.first;
+            const uint64_t d = it->second.second;
+            if (bits[f].empty()) bits[f] = doc_bits(f);
+            const double P = positions_per_file ? (double)(*positions_per_file)[f]
+                                                : (double)query_length - (double)info[f].term_size + 1.0 - (double)z;
+            out[i] = fpr_adjust(result[i].score, P, bits[f][d], cobs_gpu_signature_size(ix_, f, page_of(info[f], d)),
+                                info[f].num_hashes, z);
+        }
+        return out;
+    }
+
     //! findere z (0..7, beyond the reference): a position scores only when its z + 1 consecutive terms are all present
     //! (cobs_gpu_set_findere); 0 = the reference's count
     void set_findere(unsigned z) { check(cobs_gpu_set_findere(ix_, z)); }
@@ -391,8 +460,19 @@ private:
         for (const auto& i : indices) out.push_back(i->path());
         return out;
     }
+    static uint32_t page_of(const cobs_gpu_index_info& info, uint64_t doc) {
+        return info.kind == 0 ? 0u : (uint32_t)(doc / (8 * info.page_size));
+    }
+    cobs_gpu_index_info whole_file_info(size_t file_no) const {
+        cobs_gpu_index_info info;
+        check(cobs_gpu_info(ix_, file_no, &info));
+        if (info.slot_begin != 0 || info.slot_count < info.num_docs)
+            throw Error(COBS_GPU_ERR_UNSUPPORTED, "this handle holds a shard of the file's documents: use doc_bits");
+        return info;
+    }
     cobs_gpu_index* ix_ = nullptr;
     std::vector<cobs_gpu_hit> hits_;
+    std::unordered_map<const char*, std::pair<size_t, uint64_t>> doc_of_name_;      // adjust(): built on first use
 };
 
 //! The same operator over SEVERAL GPUs of one node, one process: the index is sharded by
