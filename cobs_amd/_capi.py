@@ -162,6 +162,9 @@ SYMBOLS = {
     "cobs_gpu_hit_positions": (_int, [_vp, C.POINTER(_cp), C.POINTER(_sz), _sz, C.POINTER(Hit), C.POINTER(_sz),
                                       _pu64, _sz, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz)]),
     "cobs_gpu_positions_ms": (_int, [_vp, C.POINTER(C.c_double * 3)]),
+    "cobs_gpu_prevalence": (_int, [_vp, C.POINTER(_cp), C.POINTER(_sz), _sz, C.POINTER(_u32), _sz, C.POINTER(_sz),
+                                   C.POINTER(_sz), C.POINTER(_sz)]),
+    "cobs_gpu_prevalence_ms": (_int, [_vp, C.POINTER(C.c_double * 3)]),
     "cobs_gpu_search_groups": (_int, [_vp, C.POINTER(_cp), C.POINTER(_sz), _sz, C.POINTER(_sz), _sz, _dbl, _dbl, _sz,
                                       C.POINTER(GroupHit), _sz, C.POINTER(_sz), _pu64, C.POINTER(_sz)]),
     "cobs_gpu_groups_ms": (_int, [_vp, C.POINTER(C.c_double * 3)]),

@@ -30,7 +30,7 @@
 static void usage() {
     std::fprintf(stderr,
                  "usage: cobs_gpu_query -i INDEX [-i INDEX ...] [-t THRESHOLD] [-l LIMIT] "
-                 "[-d DEVICE[,DEVICE...]] [--hbm-budget GIB] [--findere Z] [--invalid-bases MODE] [--positions] [--fpr-adjust] (QUERY | -f QUERY_FILE)\n"
+                 "[-d DEVICE[,DEVICE...]] [--hbm-budget GIB] [--findere Z] [--invalid-bases MODE] [--positions] [--prevalence] [--fpr-adjust] (QUERY | -f QUERY_FILE)\n"
                  "       cobs_gpu_query doc-stats INDEX [--fill-above X]\n"
                  "         one line per document: file, name, sub-index, S_p, bits set in its filter, fill = bits / S_p, fpr = fill^H\n"
                  "       --fpr-adjust: every result line gets expected_fp (the positions the document's fill alone is expected to\n"
@@ -43,6 +43,10 @@ static void usage() {
                  "       --positions: every result line gets a tab and one character per position of the query in that\n"
                  "        document, position 0 first: 1 = the k-mer there (with --findere Z: all Z + 1 from there) is present;\n"
                  "        the number of 1s is the score.  Not with several devices or --hbm-budget.\n"
+                 "       --prevalence: instead of results, per query its *comment line (with the number of index files) and one\n"
+                 "        line per index file: file_no<TAB>num_docs<TAB>n<TAB>c0 c1 ... c(n-1), c_p = the documents of the file\n"
+                 "        that hold position p of the query (honours --findere and --invalid-bases).  Not with several devices\n"
+                 "        or --hbm-budget.\n"
                  "       --findere Z (0..7): a k-mer position scores only when Z + 1 consecutive k-mers are all present\n"
                  "        (findere, beyond `cobs query`: far fewer false-positive k-mers; a query needs k + Z characters)\n"
                  "       --invalid-bases error|miss|skip: a character outside ACGT fails the call (error, the default, as `cobs query`\n"
@@ -195,6 +199,33 @@ static void print_with_positions(cobs_gpu::ClassicSearch& s, const std::vector<s
     }
 }
 
+// --prevalence: per query its comment line and one line per index file: file_no, documents, positions, the counts
+static void print_prevalence(cobs_gpu::ClassicSearch& s, const std::vector<std::string>& queries, const std::vector<std::string>* comments) {
+    std::vector<uint32_t> counts;
+    std::vector<size_t> offs;
+    s.prevalence(queries, counts, offs);
+    const size_t nf = cobs_gpu_num_files(s.handle());
+    std::vector<uint64_t> num_docs(nf);
+    for (size_t f = 0; f < nf; ++f) {
+        cobs_gpu_index_info info;
+        if (cobs_gpu_info(s.handle(), f, &info) != COBS_GPU_OK) throw cobs_gpu::Error(COBS_GPU_ERR_ARG, cobs_gpu_last_error());
+        num_docs[f] = info.num_docs;
+    }
+    std::string line;
+    for (size_t q = 0; q < queries.size(); ++q) {
+        if (comments) std::cout << (*comments)[q] << '\t' << nf << '\n';
+        for (size_t f = 0; f < nf; ++f) {
+            const size_t a = offs[q * nf + f], b = offs[q * nf + f + 1];
+            line = std::to_string(f) + '\t' + std::to_string(num_docs[f]) + '\t' + std::to_string(b - a) + '\t';
+            for (size_t i = a; i < b; ++i) {
+                if (i > a) line += ' ';
+                line += std::to_string(counts[i]);
+            }
+            std::cout << line << '\n';
+        }
+    }
+}
+
 // --fpr-adjust: "\texpected_fp\tadjusted" of every result of one query.  Under --invalid-bases skip the positions are the
 // query's valid ones per file, read from a device batch of that one query (cobs_gpu_batch_scored_positions).
 static std::vector<cobs_gpu::ClassicSearch::Adjusted> adjusted_of(cobs_gpu::ClassicSearch& s, const std::string& query,
@@ -290,6 +321,7 @@ int main(int argc, char** argv) {
     int findere = -1;                        // --findere Z; -1: not given (the handle's default, 0)
     unsigned invalid_bases = COBS_GPU_INVALID_ERROR;   // --invalid-bases MODE
     bool positions = false;                  // --positions
+    bool prevalence = false;                 // --prevalence
     bool fpr_adjust = false;                 // --fpr-adjust
     std::string group;                       // --group N|all
     double read_threshold = 0.0;             // --read-threshold X
@@ -348,6 +380,7 @@ int main(int argc, char** argv) {
             else { std::fprintf(stderr, "--invalid-bases: error, miss or skip\n"); return 1; }
         }
         else if (a == "--positions") positions = true;
+        else if (a == "--prevalence") prevalence = true;
         else if (a == "--fpr-adjust") fpr_adjust = true;
         else if (a == "--group") group = need("--group");
         else if (a == "--read-threshold") read_threshold = std::atof(need("--read-threshold"));
@@ -360,6 +393,11 @@ int main(int argc, char** argv) {
     if (positions && (devices.size() > 1 || force_sharded || hbm_budget != 0)) {
         std::fprintf(stderr, "--positions: not with several devices (-d A,B / --sharded) or --hbm-budget: "
                              "the rows of a document have to be resident on one GPU\n");
+        return 1;
+    }
+    if (prevalence && (devices.size() > 1 || force_sharded || hbm_budget != 0 || positions || fpr_adjust || !group.empty())) {
+        std::fprintf(stderr, "--prevalence: not with several devices (-d A,B / --sharded) or --hbm-budget (the rows have to be "
+                             "resident on one GPU), nor with --positions, --fpr-adjust or --group\n");
         return 1;
     }
     size_t group_size = 0;                   // 0 with --group all
@@ -452,6 +490,12 @@ int main(int argc, char** argv) {
     try {
         std::unique_ptr<cobs_gpu::BatchSearch> sp = open_index();
         cobs_gpu::BatchSearch& s = *sp;
+        if (!query_line.empty() && prevalence) {
+            print_prevalence(dynamic_cast<cobs_gpu::ClassicSearch&>(s), {query_line}, nullptr);
+            std::cout.flush();
+            print_timer(s);
+            return 0;
+        }
         if (!query_line.empty() && positions) {
             print_with_positions(dynamic_cast<cobs_gpu::ClassicSearch&>(s), {query_line}, nullptr, threshold, num_results, fpr_adjust);
             std::cout.flush();
@@ -485,6 +529,12 @@ int main(int argc, char** argv) {
             }
         }
         if (!query.empty()) { queries.push_back(query); comments.push_back(comment); }
+        if (prevalence) {
+            print_prevalence(dynamic_cast<cobs_gpu::ClassicSearch&>(s), queries, &comments);
+            std::cout.flush();
+            print_timer(s);
+            return 0;
+        }
         if (!group.empty()) {
             std::vector<size_t> offs{0};
             const size_t step = group_size ? group_size : std::max<size_t>(queries.size(), 1);

@@ -158,6 +158,7 @@ cobs_gpu_index::~cobs_gpu_index() {
     if (positions) destroy_positions_work(positions);
     if (groups) destroy_groups_work(groups);
     if (fill) destroy_fill_work(fill);
+    if (prevalence) destroy_prevalence_work(prevalence);
     for (auto* b : scratch) delete b;
     if (xchg_stream) (void)hipStreamDestroy(xchg_stream);
 }

@@ -698,6 +698,48 @@ class Search:
                         unpack_positions(bits[int(bit_offsets[i]):int(bit_offsets[i + 1])], n)))
         return out
 
+    # -- prevalence: HOW MANY documents hold each position of a query ---------------
+    def prevalence_arrays(self, queries):
+        """cobs_gpu_prevalence -> (offsets uint64 [nq * num_files + 1], counts uint32): segment (q, f) is
+        counts[offsets[q * num_files + f]:offsets[q * num_files + f + 1]], one count per position of query q in file f
+        (n = T_f - findere): the real documents of the file in which terms p .. p + findere are all present.  On one shard
+        of several the counts cover the shard's own documents; the parts of all shards add up."""
+        if type(self)._search_batch_call is not Search._search_batch_call:
+            raise CobsGpuError(_capi.ERR_UNSUPPORTED, "prevalence: not on a device-list handle (ask the shards: shard(rank).prevalence, and add)")
+        qs = [q if type(q) is bytes else _as_bytes(q) for q in queries]
+        nq = len(qs)
+        arr = (C.c_char_p * max(nq, 1))(*qs)
+        lens = (C.c_size_t * max(nq, 1))(*[len(q) for q in qs])
+        offsets = np.zeros(nq * self.num_files + 1, dtype=np.uint64)
+        need, bad = C.c_size_t(0), C.c_size_t(0)
+        # the number of cells is host arithmetic (the call refuses a buffer that is too small before any device work)
+        counts = np.zeros(0, dtype=np.uint32)
+        while True:
+            st = self._lib.cobs_gpu_prevalence(
+                self._h, arr, lens, nq, C.cast(counts.ctypes.data, C.POINTER(C.c_uint32)), counts.size,
+                C.cast(offsets.ctypes.data, C.POINTER(C.c_size_t)), C.byref(need), C.byref(bad))
+            if st == _capi.ERR_CAPACITY and need.value > counts.size:
+                counts = np.zeros(need.value, dtype=np.uint32)
+                continue
+            check(st)
+            break
+        return offsets, counts
+
+    def prevalence(self, queries):
+        """per query a list with one uint32 array per file (prevalence_arrays, cut up); one str / bytes query -> its list"""
+        single = isinstance(queries, (str, bytes, bytearray))
+        qs = [queries] if single else list(queries)
+        offsets, counts = self.prevalence_arrays(qs)
+        nf = self.num_files
+        out = [[counts[int(offsets[q * nf + f]):int(offsets[q * nf + f + 1])] for f in range(nf)] for q in range(len(qs))]
+        return out[0] if single else out
+
+    def prevalence_ms(self):
+        """kernel times of the prevalence calls since the previous call of this method (HIP events, summed over passes)"""
+        t = (C.c_double * 3)()
+        check(self._lib.cobs_gpu_prevalence_ms(self._h, C.byref(t)))
+        return {"kernel_ms": t[0], "hash_ms": t[1], "passes": int(t[2])}
+
     # -- grouped search: which documents a SET of queries comes from -----------------
     GROUP_HIT_DTYPE = np.dtype([("file_no", "<u4"), ("doc", "<u4"), ("score", "<u4"), ("votes", "<u4")])
 

@@ -167,6 +167,29 @@ cobs_gpu_status cobs_gpu_search_groups(cobs_gpu_index* ix, const char* const* qu
  * counterpart: ask the shards (cobs_gpu_multi_index). */
 cobs_gpu_status cobs_gpu_doc_bits(cobs_gpu_index* ix, size_t file_no, uint64_t* bits, size_t cap, size_t* needed);
 
+/* ---- query prevalence ---------------------------------------------------- */
+/* For every position of a query, HOW MANY documents hold it, beyond the reference: the profile along the query (a
+ * conservation track of a gene, the core and accessory stretches of a contig, the ubiquitous k-mers that inflate every
+ * score of a read).  With T = len - term_size(file) + 1 terms and the handle's findere z a query has n = T - z positions in
+ * a file; position p is set in document d when terms p .. p + z are all present in d (every term: all of the file's hash
+ * bits set in d's column, as the scan counts it).  counts[offsets[q * n_files + f] + p] = the REAL documents of file f in
+ * which position p of query q is set; padding slots never count, whatever bits a file holds there.  Segment (q, f) is
+ * counts[offsets[q * n_files + f] .. offsets[q * n_files + f + 1]) -- offsets has nq * n_files + 1 entries.  Under
+ * COBS_GPU_INVALID_MISS / _SKIP a position whose window holds a character outside ACGT is 0; under _ERROR the call fails
+ * as a search does.  The sum of a segment equals the sum over the file's real documents of the scores a search reports
+ * for q, and counts[..p] equals the hits whose cobs_gpu_hit_positions bit p is set.
+ * On one shard of several the counts cover the documents of the shard's own slots: they are additive, the parts of all
+ * shards add up to the unsharded answer.  One gather over the resident rows, as the scan's, reduced across documents.
+ * Everything the host can refuse is refused before any device work: COBS_GPU_ERR_ARG (NULL arguments),
+ * COBS_GPU_ERR_QUERY_TOO_SHORT / _TOO_LONG (*bad_query = the offending query), COBS_GPU_ERR_CAPACITY when cap is too small
+ * -- offsets and *needed (optional) are filled, so the call can be repeated (counts may be NULL when cap is 0) --,
+ * COBS_GPU_ERR_UNSUPPORTED on a handle opened with an HBM budget (its rows are not all resident).
+ * COBS_GPU_ERR_INVALID_BASE comes from the device (*bad_query).  The device list (cobs_gpu_multi_*) has no counterpart:
+ * ask the shards (cobs_gpu_multi_index) and add. */
+/* offsets: nq * nfiles + 1 entries; segment (q, f) = counts[offsets[q*nfiles+f] .. offsets[q*nfiles+f+1]), length T_f - z */
+cobs_gpu_status cobs_gpu_prevalence(cobs_gpu_index* ix, const char* const* queries, const size_t* lens, size_t nq,
+                                    uint32_t* counts, size_t cap, size_t* offsets, size_t* needed, size_t* bad_query);
+
 /* score slots per query held by THIS shard (== cobs_gpu_total_counts when
  * unsharded); device count rows have this many elements */
 uint64_t cobs_gpu_local_counts(const cobs_gpu_index* ix);

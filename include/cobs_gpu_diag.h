@@ -79,6 +79,10 @@ cobs_gpu_status cobs_gpu_batch_kernel_ms(cobs_gpu_batch* b, float* scan_ms, floa
  * this function, summed over their passes: out[0] = the presence kernel, out[1] = K1 (hashing), out[2] = passes. */
 cobs_gpu_status cobs_gpu_positions_ms(cobs_gpu_index* ix, double out[3]);
 
+/* HIP-event durations (ms) of the kernels of the cobs_gpu_prevalence calls on this handle since the previous call of this
+ * function, summed over their passes: out[0] = the prevalence kernel, out[1] = K1 (hashing), out[2] = passes. */
+cobs_gpu_status cobs_gpu_prevalence_ms(cobs_gpu_index* ix, double out[3]);
+
 /* Durations (ms) of the LAST cobs_gpu_search_groups call on this handle: out[0] = the accumulate kernel (HIP events, summed
  * over the call's passes), out[1] = the select kernel (HIP events), out[2] = the host's ordering of the records. */
 cobs_gpu_status cobs_gpu_groups_ms(cobs_gpu_index* ix, double out[3]);

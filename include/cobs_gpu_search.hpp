@@ -327,6 +327,25 @@ public:
         }
     }
 
+    //! for every position of every query, how many documents hold it (beyond the reference; cobs_gpu_prevalence): segment
+    //! (q, f) of file f is counts[offsets[q * n_files + f] .. offsets[q * n_files + f + 1]), one count per position of the
+    //! query's n = T_f - z; on one shard of several the documents of the shard's own slots (the parts add up)
+    void prevalence(const std::vector<std::string>& queries, std::vector<uint32_t>& counts, std::vector<size_t>& offsets) {
+        std::vector<const char*> qp;
+        std::vector<size_t> ql;
+        for (const auto& q : queries) { qp.push_back(q.data()); ql.push_back(q.size()); }
+        const size_t nq = queries.size();
+        offsets.assign(nq * cobs_gpu_num_files(ix_) + 1, 0);
+        counts.clear();
+        size_t bad = 0, need = 0;
+        cobs_gpu_status st = cobs_gpu_prevalence(ix_, qp.data(), ql.data(), nq, nullptr, 0, offsets.data(), &need, &bad);
+        if (st == COBS_GPU_ERR_CAPACITY && need > 0) {       // the size is host arithmetic: nothing has run yet
+            counts.resize(need);
+            st = cobs_gpu_prevalence(ix_, qp.data(), ql.data(), nq, counts.data(), counts.size(), offsets.data(), &need, &bad);
+        }
+        check(st);
+    }
+
     //! one document of a group's result: the sum of the scores of the group's queries and how many of them it was a hit of
     struct GroupResult {
         const char* doc_name;
