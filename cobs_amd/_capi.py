@@ -165,6 +165,10 @@ SYMBOLS = {
     "cobs_gpu_prevalence": (_int, [_vp, C.POINTER(_cp), C.POINTER(_sz), _sz, C.POINTER(_u32), _sz, C.POINTER(_sz),
                                    C.POINTER(_sz), C.POINTER(_sz)]),
     "cobs_gpu_prevalence_ms": (_int, [_vp, C.POINTER(C.c_double * 3)]),
+    "cobs_gpu_idf_weight": (_u32, [_u64, _u64]),
+    "cobs_gpu_search_weighted": (_int, [_vp, C.POINTER(_cp), C.POINTER(_sz), _sz, _dbl, _sz, C.POINTER(Hit), _sz,
+                                        C.POINTER(_sz), _pu64, C.POINTER(_sz)]),
+    "cobs_gpu_weighted_ms": (_int, [_vp, C.POINTER(C.c_double * 5)]),
     "cobs_gpu_search_groups": (_int, [_vp, C.POINTER(_cp), C.POINTER(_sz), _sz, C.POINTER(_sz), _sz, _dbl, _dbl, _sz,
                                       C.POINTER(GroupHit), _sz, C.POINTER(_sz), _pu64, C.POINTER(_sz)]),
     "cobs_gpu_groups_ms": (_int, [_vp, C.POINTER(C.c_double * 3)]),

@@ -30,7 +30,7 @@
 static void usage() {
     std::fprintf(stderr,
                  "usage: cobs_gpu_query -i INDEX [-i INDEX ...] [-t THRESHOLD] [-l LIMIT] "
-                 "[-d DEVICE[,DEVICE...]] [--hbm-budget GIB] [--findere Z] [--invalid-bases MODE] [--positions] [--prevalence] [--fpr-adjust] (QUERY | -f QUERY_FILE)\n"
+                 "[-d DEVICE[,DEVICE...]] [--hbm-budget GIB] [--findere Z] [--invalid-bases MODE] [--positions] [--prevalence] [--weighted] [--fpr-adjust] (QUERY | -f QUERY_FILE)\n"
                  "       cobs_gpu_query doc-stats INDEX [--fill-above X]\n"
                  "         one line per document: file, name, sub-index, S_p, bits set in its filter, fill = bits / S_p, fpr = fill^H\n"
                  "       --fpr-adjust: every result line gets expected_fp (the positions the document's fill alone is expected to\n"
@@ -47,6 +47,11 @@ static void usage() {
                  "        line per index file: file_no<TAB>num_docs<TAB>n<TAB>c0 c1 ... c(n-1), c_p = the documents of the file\n"
                  "        that hold position p of the query (honours --findere and --invalid-bases).  Not with several devices\n"
                  "        or --hbm-budget.\n"
+                 "       --weighted: IDF-weighted search -- a k-mer held by c of a file's D documents weighs 1 + min(14,\n"
+                 "        floor(log2(D / c))) (0 when nobody holds it), a document scores the sum of the weights of the k-mers it\n"
+                 "        holds and is a hit when that reaches -t of the query's total weight; same output as a plain query with\n"
+                 "        the weighted score in place of the count (honours -l, --findere and --invalid-bases).  Not with several\n"
+                 "        devices or --hbm-budget.\n"
                  "       --findere Z (0..7): a k-mer position scores only when Z + 1 consecutive k-mers are all present\n"
                  "        (findere, beyond `cobs query`: far fewer false-positive k-mers; a query needs k + Z characters)\n"
                  "       --invalid-bases error|miss|skip: a character outside ACGT fails the call (error, the default, as `cobs query`\n"
@@ -322,6 +327,7 @@ int main(int argc, char** argv) {
     unsigned invalid_bases = COBS_GPU_INVALID_ERROR;   // --invalid-bases MODE
     bool positions = false;                  // --positions
     bool prevalence = false;                 // --prevalence
+    bool weighted = false;                   // --weighted
     bool fpr_adjust = false;                 // --fpr-adjust
     std::string group;                       // --group N|all
     double read_threshold = 0.0;             // --read-threshold X
@@ -381,6 +387,7 @@ int main(int argc, char** argv) {
         }
         else if (a == "--positions") positions = true;
         else if (a == "--prevalence") prevalence = true;
+        else if (a == "--weighted") weighted = true;
         else if (a == "--fpr-adjust") fpr_adjust = true;
         else if (a == "--group") group = need("--group");
         else if (a == "--read-threshold") read_threshold = std::atof(need("--read-threshold"));
@@ -398,6 +405,12 @@ int main(int argc, char** argv) {
     if (prevalence && (devices.size() > 1 || force_sharded || hbm_budget != 0 || positions || fpr_adjust || !group.empty())) {
         std::fprintf(stderr, "--prevalence: not with several devices (-d A,B / --sharded) or --hbm-budget (the rows have to be "
                              "resident on one GPU), nor with --positions, --fpr-adjust or --group\n");
+        return 1;
+    }
+    if (weighted && (devices.size() > 1 || force_sharded || hbm_budget != 0 || positions || prevalence || fpr_adjust || !group.empty())) {
+        std::fprintf(stderr, "--weighted: not with several devices (-d A,B / --sharded: the weights need every shard's counts) or "
+                             "--hbm-budget (the rows have to be resident on one GPU), nor with --positions, --prevalence, "
+                             "--fpr-adjust or --group\n");
         return 1;
     }
     size_t group_size = 0;                   // 0 with --group all
@@ -496,6 +509,14 @@ int main(int argc, char** argv) {
             print_timer(s);
             return 0;
         }
+        if (!query_line.empty() && weighted) {
+            std::vector<std::vector<cobs_gpu::SearchResult>> results;
+            dynamic_cast<cobs_gpu::ClassicSearch&>(s).search_weighted({query_line}, results, threshold, num_results);
+            for (const auto& r : results[0]) std::cout << r.doc_name << '\t' << r.score << '\n';
+            std::cout.flush();
+            print_timer(s);
+            return 0;
+        }
         if (!query_line.empty() && positions) {
             print_with_positions(dynamic_cast<cobs_gpu::ClassicSearch&>(s), {query_line}, nullptr, threshold, num_results, fpr_adjust);
             std::cout.flush();
@@ -531,6 +552,17 @@ int main(int argc, char** argv) {
         if (!query.empty()) { queries.push_back(query); comments.push_back(comment); }
         if (prevalence) {
             print_prevalence(dynamic_cast<cobs_gpu::ClassicSearch&>(s), queries, &comments);
+            std::cout.flush();
+            print_timer(s);
+            return 0;
+        }
+        if (weighted) {
+            std::vector<std::vector<cobs_gpu::SearchResult>> results;
+            dynamic_cast<cobs_gpu::ClassicSearch&>(s).search_weighted(queries, results, threshold, num_results);
+            for (size_t q = 0; q < queries.size(); ++q) {
+                std::cout << comments[q] << '\t' << results[q].size() << '\n';
+                for (const auto& r : results[q]) std::cout << r.doc_name << '\t' << r.score << '\n';
+            }
             std::cout.flush();
             print_timer(s);
             return 0;

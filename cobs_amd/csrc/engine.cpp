@@ -159,6 +159,7 @@ cobs_gpu_index::~cobs_gpu_index() {
     if (groups) destroy_groups_work(groups);
     if (fill) destroy_fill_work(fill);
     if (prevalence) destroy_prevalence_work(prevalence);
+    if (weighted) destroy_weighted_work(weighted);
     for (auto* b : scratch) delete b;
     if (xchg_stream) (void)hipStreamDestroy(xchg_stream);
 }

@@ -1,0 +1,387 @@
+// cobs_amd/csrc/weighted.cpp -- cobs_gpu_search_weighted: a search whose score is the sum of IDF weights of the positions
+// a document holds.  Per device pass (cut by the workspace limit, on the handle's scratch batch): K1 hashes the queries
+// (unchanged: findere and the invalid-bases policy live in its table), the prevalence kernel counts the documents of
+// every position into device cells, the weight kernel turns the cells into one byte per position plus W(q, f) and the
+// threshold of every (query, file), and the weighted scan appends the documents that reach it to a pool
+// (weighted_kernels.hip).  A pool that overflows is grown to the fill the scan reports and the scan of that pass alone
+// runs again.  The host orders every query's records and cuts them to num_results, as groups.cpp does for its groups.
+#include <hip/hip_runtime_api.h>
+
+#include <algorithm>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "engine.hpp"
+#include "prevalence_kernels.hpp"
+#include "weighted_kernels.hpp"
+
+namespace cobs_amd {
+
+struct WeightedWork {
+    DevBuf<uint32_t> cells;
+    DevBuf<uint8_t> weights;
+    DevBuf<uint64_t> seg_off, total;
+    DevBuf<uint32_t> thr;                   // [file][nq]
+    DevBuf<HitDev> pool;
+    DevBuf<unsigned long long> fill;
+    PinnedBuf<uint64_t> h_seg_off, h_total;
+    PinnedBuf<uint32_t> h_flags;            // K1's flag words | the pool's 64-bit fill
+    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // before K1 | prevalence | weights | scan | after it
+    double ms[4] = {0, 0, 0, 0};            // hash | prevalence | weights | scan
+    uint64_t passes = 0;
+    ~WeightedWork() {
+        for (auto& e : ev) if (e) (void)hipEventDestroy(e);
+    }
+};
+
+void destroy_weighted_work(WeightedWork* w) { delete w; }
+
+namespace {
+
+struct Call {
+    cobs_gpu_index* ix;
+    const char* const* queries;
+    const size_t* lens;
+    double threshold;
+    uint64_t* total_weight;
+    size_t* bad_query;
+    uint32_t z;
+    uint64_t real_total;                    // real documents of all files
+    std::vector<HitDev>* recs;              // the records of all passes, `query` = the call's query number
+};
+
+// the scan of the pass's queries over every resident chunk, into the pool
+cobs_gpu_status launch_scans(const Call& c, WeightedWork* w, cobs_gpu_batch* b, size_t n, size_t max_len, uint64_t pool_cap,
+                             hipStream_t st) {
+    cobs_gpu_index* ix = c.ix;
+    const size_t nf = ix->parts.size();
+    for (size_t f = 0; f < nf; ++f) {
+        const Part& p = ix->parts[f];
+        WeightedScanArgs sa{};
+        sa.table = b->work[f].table.p;
+        sa.blk_off = b->work[f].blk_off;
+        sa.q_len = b->d_qlen;
+        sa.seg_off = w->seg_off.p + f;
+        sa.weights = w->weights.p;
+        sa.thr = w->thr.p + f * n;
+        sa.pool = w->pool.p;
+        sa.fill = w->fill.p;
+        sa.cap = pool_cap;
+        sa.seg_stride = (uint32_t)nf;
+        sa.nq = (uint32_t)n;
+        sa.table_npages = p.num_tpages();
+        sa.num_hashes = (uint32_t)p.meta.num_hashes;
+        sa.term_size = p.meta.term_size;
+        sa.findere = c.z;
+        sa.num_docs = (uint32_t)p.meta.doc_names.size();
+        sa.file_no = (uint32_t)f;
+        sa.idx64 = p.idx64 ? 1u : 0u;
+        const int planes = weighted_planes_for(max_len - p.meta.term_size + 1 - c.z);
+        for (const Chunk& ch : p.chunks) {
+            if (!ch.d_data || ch.pages.empty()) continue;
+            sa.data = ch.d_data;
+            sa.pages = ch.d_pages;
+            sa.pitch = ch.pitch;
+            sa.cpp = ch.cpp;
+            sa.total_chunks = ch.total_chunks;
+            sa.tile_w = weighted_tile_w(ch.total_chunks);
+            HIP_TRY(launch_weighted_scan(sa, planes, st));
+        }
+    }
+    return COBS_GPU_OK;
+}
+
+// one device pass over the queries [q0, q1)
+cobs_gpu_status run_pass(const Call& c, size_t q0, size_t q1) {
+    cobs_gpu_index* ix = c.ix;
+    HIP_TRY(hipSetDevice(ix->device));
+    if (!ix->weighted) ix->weighted = new WeightedWork;
+    WeightedWork* w = ix->weighted;
+    for (auto& e : w->ev) if (!e) HIP_TRY(hipEventCreate(&e));
+    if (!ix->scratch[0]) {          // the workspace of the host-buffer calls (host_api.cpp): query upload and K1's tables
+        cobs_gpu_status st = cobs_gpu_batch_create(ix, 0, 0, &ix->scratch[0]);
+        if (st != COBS_GPU_OK) return st;
+        HIP_TRY(hipStreamCreateWithFlags(&ix->scratch[0]->own_stream, hipStreamNonBlocking));
+        HIP_TRY(hipEventCreateWithFlags(&ix->scratch[0]->done, hipEventDisableTiming));
+    }
+    cobs_gpu_batch* b = ix->scratch[0];
+    hipStream_t st = b->own_stream;
+    const size_t n = q1 - q0, nf = ix->parts.size();
+    size_t bad_local = 0;
+    if (cobs_gpu_status s = set_queries_on(b, c.queries + q0, c.lens + q0, n, st, false, &bad_local, q0); s != COBS_GPU_OK) {
+        if (c.bad_query && bad_local < n) *c.bad_query = q0 + bad_local;
+        return s;
+    }
+    // the cells of the pass: one segment per (query, file), each padded to a multiple of 8 -- the scan reads the eight
+    // weights of a block with one aligned load, the padding weighs 0
+    HIP_TRY(w->seg_off.reserve(n * nf + 1));
+    HIP_TRY(w->h_seg_off.reserve(n * nf + 1));
+    uint64_t ncells = 0;
+    size_t max_len = 0;
+    for (size_t q = q0; q < q1; ++q) {
+        max_len = std::max(max_len, c.lens[q]);
+        for (size_t f = 0; f < nf; ++f) {
+            w->h_seg_off.p[(q - q0) * nf + f] = ncells;
+            ncells += round_up(c.lens[q] - ix->parts[f].meta.term_size + 1 - c.z, 8);
+        }
+    }
+    w->h_seg_off.p[n * nf] = ncells;
+    HIP_TRY(w->cells.reserve(ncells));
+    HIP_TRY(w->weights.reserve(ncells));
+    HIP_TRY(w->total.reserve(n * nf));
+    HIP_TRY(w->h_total.reserve(n * nf));
+    HIP_TRY(w->thr.reserve(n * nf));
+    HIP_TRY(w->fill.reserve(1));
+    HIP_TRY(w->h_flags.reserve(6));
+    // the first guess of the pool (tuning key hit_cap: a small one, so that tests reach the overflow path)
+    const uint64_t all = c.real_total * n;
+    uint64_t pool_cap = c.threshold > 0.0 ? std::min<uint64_t>(all, std::max<uint64_t>(1u << 20, n * 1024ull)) : all;
+    if (ix->tune.hit_cap) pool_cap = std::min<uint64_t>(pool_cap, ix->tune.hit_cap);
+    pool_cap = std::max<uint64_t>(pool_cap, 1);
+    auto reserve_pool = [&]() -> cobs_gpu_status {
+        if (w->pool.reserve((size_t)pool_cap) != hipSuccess) {
+            (void)hipGetLastError();
+            // (not ERR_CAPACITY: that status promises the needed size of the CALLER's buffer in hit_offsets)
+            return fail(COBS_GPU_ERR_HIP, "out of device memory for " + std::to_string(pool_cap) + " hit records; raise the threshold or use fewer queries per call");
+        }
+        return COBS_GPU_OK;
+    };
+    if (cobs_gpu_status s = reserve_pool(); s != COBS_GPU_OK) return s;
+
+    HIP_TRY(hipMemcpyAsync(w->seg_off.p, w->h_seg_off.p, (n * nf + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(launch_clear_flags(b->flags.p, st));
+    HIP_TRY(launch_prevalence_zero(w->cells.p, ncells, st));
+    HIP_TRY(launch_prevalence_zero(reinterpret_cast<uint32_t*>(w->fill.p), 2, st));
+    HIP_TRY(hipEventRecord(w->ev[0], st));
+    for (size_t f = 0; f < nf; ++f) {
+        const Part& p = ix->parts[f];
+        if (p.num_tpages() == 0) continue;
+        HashArgs ha;
+        ha.text = b->d_text;
+        ha.span_off = b->d_span_off;
+        ha.q_len = b->d_qlen;
+        ha.blk_off = b->work[f].blk_off;
+        ha.pages = p.d_tpages;
+        ha.table = b->work[f].table.p;
+        ha.err_query = b->flags.p;
+        ha.nq = (uint32_t)n;
+        ha.npages = p.num_tpages();
+        ha.term_size = p.meta.term_size;
+        ha.canonicalize = p.meta.canonicalize;
+        ha.num_hashes = (uint32_t)p.meta.num_hashes;
+        ha.idx64 = p.idx64 ? 1u : 0u;
+        ha.invalid_bases = ix->invalid_bases;     // (miss / skip: a position whose window holds an invalid character reads 0)
+        ha.findere = c.z;
+        ha.valid = nullptr;
+        HIP_TRY(launch_hash(ha, round_up(b->span_off[n], 1024), st));
+    }
+    HIP_TRY(hipEventRecord(w->ev[1], st));
+    for (size_t f = 0; f < nf; ++f) {
+        const Part& p = ix->parts[f];
+        PrevalenceArgs pa{};
+        pa.table = b->work[f].table.p;
+        pa.blk_off = b->work[f].blk_off;
+        pa.q_len = b->d_qlen;
+        pa.seg_off = w->seg_off.p + f;
+        pa.out = w->cells.p;
+        pa.seg_stride = (uint32_t)nf;
+        pa.table_npages = p.num_tpages();
+        pa.num_hashes = (uint32_t)p.meta.num_hashes;
+        pa.term_size = p.meta.term_size;
+        pa.findere = c.z;
+        pa.num_docs = (uint32_t)p.meta.doc_names.size();
+        pa.idx64 = p.idx64 ? 1u : 0u;
+        const uint32_t max_positions = (uint32_t)(max_len - p.meta.term_size + 1 - c.z);
+        for (const Chunk& ch : p.chunks) {
+            if (!ch.d_data || ch.pages.empty()) continue;
+            pa.data = ch.d_data;
+            pa.pages = ch.d_pages;
+            pa.pitch = ch.pitch;
+            HIP_TRY(launch_prevalence(pa, ch.pages, (uint32_t)n, max_positions, st));
+        }
+    }
+    HIP_TRY(hipEventRecord(w->ev[2], st));
+    for (size_t f = 0; f < nf; ++f) {
+        const Part& p = ix->parts[f];
+        WeightArgs wa{};
+        wa.cells = w->cells.p;
+        wa.weights = w->weights.p;
+        wa.seg_off = w->seg_off.p + f;
+        wa.q_len = b->d_qlen;
+        wa.total = w->total.p + f;
+        wa.thr = w->thr.p + f * n;
+        wa.threshold = c.threshold;
+        wa.seg_stride = (uint32_t)nf;
+        wa.term_size = p.meta.term_size;
+        wa.findere = c.z;
+        wa.num_docs = (uint32_t)p.meta.doc_names.size();
+        HIP_TRY(launch_weights(wa, (uint32_t)n, st));
+    }
+    HIP_TRY(hipEventRecord(w->ev[3], st));
+    if (cobs_gpu_status s = launch_scans(c, w, b, n, max_len, pool_cap, st); s != COBS_GPU_OK) return s;
+    HIP_TRY(hipEventRecord(w->ev[4], st));
+    HIP_TRY(hipMemcpyAsync(w->h_flags.p, b->flags.p, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(w->h_flags.p + 4, w->fill.p, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(w->h_total.p, w->total.p, n * nf * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    float t[4] = {0, 0, 0, 0};
+    bool timed = true;
+    for (int i = 0; i < 4; ++i) timed = timed && hipEventElapsedTime(&t[i], w->ev[i], w->ev[i + 1]) == hipSuccess;
+    if (timed) {
+        for (int i = 0; i < 4; ++i) w->ms[i] += t[i];
+        w->passes++;
+    } else {
+        (void)hipGetLastError();
+    }
+    if (w->h_flags.p[0] != 0u) {          // K1 keeps 2^32-1 - (first query with a non-ACGT character)
+        const size_t bad = q0 + std::min<size_t>(0xFFFFFFFFu - w->h_flags.p[0], n - 1);
+        if (c.bad_query) *c.bad_query = bad;
+        return fail(COBS_GPU_ERR_INVALID_BASE, "Invalid DNA base pair in query string. Only ACGT are allowed. (query " +
+                                               std::to_string(bad) + ")");
+    }
+    uint64_t fill = (uint64_t)w->h_flags.p[5] << 32 | w->h_flags.p[4];
+    if (fill > pool_cap) {
+        // overflow: the pool grows to the reported fill and the scan of this pass alone runs again (cells and weights stay)
+        pool_cap = fill;
+        if (cobs_gpu_status s = reserve_pool(); s != COBS_GPU_OK) return s;
+        HIP_TRY(launch_prevalence_zero(reinterpret_cast<uint32_t*>(w->fill.p), 2, st));
+        HIP_TRY(hipEventRecord(w->ev[3], st));
+        if (cobs_gpu_status s = launch_scans(c, w, b, n, max_len, pool_cap, st); s != COBS_GPU_OK) return s;
+        HIP_TRY(hipEventRecord(w->ev[4], st));
+        HIP_TRY(hipMemcpyAsync(w->h_flags.p + 4, w->fill.p, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (hipEventElapsedTime(&t[3], w->ev[3], w->ev[4]) == hipSuccess) w->ms[3] += t[3];
+        else (void)hipGetLastError();
+        fill = (uint64_t)w->h_flags.p[5] << 32 | w->h_flags.p[4];
+        if (fill > pool_cap) return fail(COBS_GPU_ERR_HIP, "weighted: the hit pool overflowed twice");
+    }
+    if (c.total_weight) std::memcpy(c.total_weight + q0 * nf, w->h_total.p, n * nf * sizeof(uint64_t));
+    const size_t at = c.recs->size();
+    c.recs->resize(at + (size_t)fill);
+    if (fill) {
+        HIP_TRY(hipMemcpy(c.recs->data() + at, w->pool.p, (size_t)fill * sizeof(HitDev), hipMemcpyDeviceToHost));
+        for (size_t i = at; i < c.recs->size(); ++i) (*c.recs)[i].query += (uint32_t)q0;
+    }
+    return COBS_GPU_OK;
+}
+
+cobs_gpu_status search_weighted_impl(cobs_gpu_index* ix, const char* const* queries, const size_t* lens, size_t nq,
+                                     double threshold, size_t num_results, cobs_gpu_hit* hits, size_t cap, size_t* hit_offsets,
+                                     uint64_t* total_weight, size_t* bad_query) {
+    if (!ix || !hit_offsets) return fail(COBS_GPU_ERR_ARG, "NULL argument");
+    if ((nq && (!queries || !lens)) || (cap && !hits)) return fail(COBS_GPU_ERR_ARG, "NULL argument");
+    if (nq >= 0xFFFFFFF0ull) return fail(COBS_GPU_ERR_ARG, "too many queries");
+    bool streamed = ix->hbm_budget != 0;
+    for (const Part& p : ix->parts) streamed = streamed || p.streamed;
+    if (streamed) return fail(COBS_GPU_ERR_UNSUPPORTED, "weighted: not on a handle with an HBM budget (its rows are not all resident)");
+    if (ix->shard_count > 1) return fail(COBS_GPU_ERR_UNSUPPORTED, "weighted: not on one shard of several (the weights need every shard's counts)");
+    for (size_t q = 0; q <= nq; ++q) hit_offsets[q] = 0;
+    const size_t nf = ix->parts.size();
+    const uint32_t z = ix->findere;
+    uint32_t max_term = 0, min_term = 0xFFFFFFFFu;
+    for (const Part& p : ix->parts) {
+        max_term = std::max(max_term, p.meta.term_size);
+        min_term = std::min(min_term, p.meta.term_size);
+    }
+    // everything the host can refuse is refused before anything is launched
+    for (size_t q = 0; q < nq; ++q) {
+        if (bad_query) *bad_query = q;
+        if (!queries[q]) return fail(COBS_GPU_ERR_ARG, "NULL query (query " + std::to_string(q) + ")");
+        if (lens[q] < (size_t)max_term + z)
+            return fail(COBS_GPU_ERR_QUERY_TOO_SHORT, "query too short, needs to be at least " + std::to_string(max_term + z) +
+                        " characters long" + (z ? " with findere z = " + std::to_string(z) : std::string()) +
+                        " (query " + std::to_string(q) + ")");
+        // 15 * n stays below 2^20, the counter planes of the scan
+        if (nf && lens[q] - min_term + 1 - z > kWeightedMaxPositions)
+            return fail(COBS_GPU_ERR_QUERY_TOO_LONG, "query too long: weighted search scores at most " +
+                        std::to_string(kWeightedMaxPositions) + " positions (query " + std::to_string(q) + ")");
+    }
+    if (bad_query) *bad_query = 0;
+    if (total_weight) std::fill(total_weight, total_weight + nq * nf, 0ull);
+    if (nq == 0 || nf == 0) return COBS_GPU_OK;
+
+    uint64_t real_total = 0;
+    for (const Part& p : ix->parts) {
+        const uint64_t docs = p.meta.doc_names.size();
+        real_total += docs > p.slot_begin ? std::min<uint64_t>(docs - p.slot_begin, p.slot_count) : 0;
+    }
+    std::vector<HitDev> recs;
+    const Call call{ix, queries, lens, threshold, total_weight, bad_query, z, real_total, &recs};
+    // passes: K1's tables, 5 bytes per position and file, and -- when every document comes back -- the pool's records stay
+    // below the search call's workspace limit
+    const uint64_t kLimit = ix->tune.pass_bytes;
+    uint64_t terms_per_char = 0;
+    for (const Part& p : ix->parts) terms_per_char += 4ull * p.meta.num_hashes * std::max<uint32_t>(p.num_tpages(), 1) * (p.idx64 ? 2 : 1);
+    const uint64_t pool_bytes = threshold > 0.0 ? 0 : real_total * sizeof(HitDev);
+    size_t first = 0;
+    uint64_t bytes = 0;
+    for (size_t q = 0; q < nq; ++q) {
+        uint64_t qb = (uint64_t)(lens[q] + 16) * terms_per_char + pool_bytes;
+        for (const Part& p : ix->parts) qb += 5ull * round_up(lens[q] - p.meta.term_size + 1 - z, 8);
+        if (q > first && bytes + qb > kLimit) {
+            if (cobs_gpu_status s = run_pass(call, first, q); s != COBS_GPU_OK) return s;
+            first = q;
+            bytes = 0;
+        }
+        bytes += qb;
+    }
+    if (cobs_gpu_status s = run_pass(call, first, nq); s != COBS_GPU_OK) return s;
+
+    // ---- ordering: per query by score descending, then (file, document) ascending; num_results cuts the list
+    std::sort(recs.begin(), recs.end(), [](const HitDev& a, const HitDev& b) {
+        if (a.query != b.query) return a.query < b.query;
+        if (a.score != b.score) return a.score > b.score;
+        if (a.part != b.part) return a.part < b.part;
+        return a.doc < b.doc;
+    });
+    std::vector<size_t> begin(nq + 1, 0);
+    for (const HitDev& r : recs) begin[r.query + 1]++;
+    for (size_t q = 0; q < nq; ++q) begin[q + 1] += begin[q];
+    size_t used = 0;
+    for (size_t q = 0; q < nq; ++q) {
+        const size_t have = begin[q + 1] - begin[q];
+        used += num_results ? std::min(have, num_results) : have;
+        hit_offsets[q + 1] = used;
+    }
+    if (used > cap) return fail(COBS_GPU_ERR_CAPACITY, "result buffer too small; hit_offsets[nq] holds the needed size");
+    for (size_t q = 0; q < nq; ++q) {
+        const HitDev* r = recs.data() + begin[q];
+        cobs_gpu_hit* out = hits + hit_offsets[q];
+        for (size_t i = 0, n = hit_offsets[q + 1] - hit_offsets[q]; i < n; ++i) out[i] = cobs_gpu_hit{r[i].part, r[i].doc, r[i].score};
+    }
+    return COBS_GPU_OK;
+}
+
+}  // namespace
+}  // namespace cobs_amd
+
+using namespace cobs_amd;
+
+extern "C" {
+
+uint32_t cobs_gpu_idf_weight(uint64_t num_docs, uint64_t count) { return idf_weight(num_docs, count); }
+
+cobs_gpu_status cobs_gpu_search_weighted(cobs_gpu_index* ix, const char* const* queries, const size_t* lens, size_t nq,
+                                         double threshold, size_t num_results, cobs_gpu_hit* hits, size_t cap,
+                                         size_t* hit_offsets, uint64_t* total_weight, size_t* bad_query) {
+    return guarded([&]() {
+        return search_weighted_impl(ix, queries, lens, nq, threshold, num_results, hits, cap, hit_offsets, total_weight, bad_query);
+    });
+}
+
+cobs_gpu_status cobs_gpu_weighted_ms(cobs_gpu_index* ix, double out[5]) {
+    if (!ix || !out) return fail(COBS_GPU_ERR_ARG, "NULL argument");
+    for (int i = 0; i < 5; ++i) out[i] = 0;
+    if (WeightedWork* w = ix->weighted) {
+        for (int i = 0; i < 4; ++i) {
+            out[i] = w->ms[i];
+            w->ms[i] = 0;
+        }
+        out[4] = (double)w->passes;
+        w->passes = 0;
+    }
+    return COBS_GPU_OK;
+}
+
+}  // extern "C"

@@ -69,6 +69,19 @@ class AdjustedResult(SearchResult):
             self.doc_name, self.score, self.expected_fp, self.adjusted)
 
 
+class WeightedResult(SearchResult):
+    """one document of a weighted result (Search.search_weighted): score = the sum of the IDF weights of the query positions
+    the document holds, total_weight = W(q, f), the sum over all positions of the query in the document's file"""
+    __slots__ = ("total_weight",)
+
+    def __init__(self, doc_name="", score=0, total_weight=0):
+        SearchResult.__init__(self, doc_name, score)
+        self.total_weight = total_weight
+
+    def __repr__(self):
+        return "WeightedResult(doc_name=%r, score=%d, total_weight=%d)" % (self.doc_name, self.score, self.total_weight)
+
+
 def fpr_adjust(score, positions, bits, sig, num_hashes, z=0):
     """What a score is worth, from the document's filter fill (host arithmetic in double, no device; scalars or arrays):
     fill = bits / sig, fpr = fill ** num_hashes (a k-mer unrelated to the document hits it), q = fpr ** (z + 1) (a findere
@@ -739,6 +752,67 @@ class Search:
         t = (C.c_double * 3)()
         check(self._lib.cobs_gpu_prevalence_ms(self._h, C.byref(t)))
         return {"kernel_ms": t[0], "hash_ms": t[1], "passes": int(t[2])}
+
+    # -- weighted search: rare k-mers count for more ---------------------------------
+    def search_weighted_arrays(self, queries, threshold=0.0, num_results=0):
+        """cobs_gpu_search_weighted -> (offsets uint64 [nq + 1], hits HIT_DTYPE, total_weight uint64 [nq, num_files]): the
+        records of query q are hits[offsets[q]:offsets[q + 1]], by weighted score descending, then (file_no, doc); a
+        position held by c of a file's D documents weighs idf_weight(D, c) = 1 + min(14, floor(log2(D / c))), 0 for
+        c = 0; a document is a hit when its score reaches max(1, ceil(threshold * total_weight[q, file]))."""
+        if type(self)._search_batch_call is not Search._search_batch_call:
+            raise CobsGpuError(_capi.ERR_UNSUPPORTED, "weighted: not on a device-list handle (the weights need every shard's counts)")
+        qs = [q if type(q) is bytes else _as_bytes(q) for q in queries]
+        nq = len(qs)
+        arr = (C.c_char_p * max(nq, 1))(*qs)
+        lens = (C.c_size_t * max(nq, 1))(*[len(q) for q in qs])
+        offs = np.zeros(nq + 1, dtype=np.uint64)
+        total = np.zeros((nq, self.num_files), dtype=np.uint64)
+        bad = C.c_size_t(0)
+        if num_results > 0:
+            cap = nq * min(int(num_results), self.total_counts)
+        elif threshold <= 0:
+            cap = nq * self.total_counts
+        else:
+            # (a buffer that proves too small costs a second run of the whole call: sized by the hits per query of the
+            # earlier thresholded weighted calls on this handle)
+            cap = max(16 * nq, int(self.__dict__.get("_weighted_hits_per_query", 0.0) * nq * 1.25)) + 1024
+        cap = max(1, cap)
+        while True:
+            hits = np.zeros(cap, dtype=self.HIT_DTYPE)
+            st = self._lib.cobs_gpu_search_weighted(
+                self._h, arr, lens, nq, float(threshold), int(num_results), C.cast(hits.ctypes.data, C.POINTER(Hit)), cap,
+                C.cast(offs.ctypes.data, C.POINTER(C.c_size_t)), C.cast(total.ctypes.data, C.POINTER(C.c_uint64)), C.byref(bad))
+            if st == _capi.ERR_CAPACITY and int(offs[nq]) > cap:
+                cap = int(offs[nq])
+                continue
+            check(st)
+            break
+        if threshold > 0 and num_results == 0 and nq:
+            self._weighted_hits_per_query = max(int(offs[nq]) / nq, 0.95 * self.__dict__.get("_weighted_hits_per_query", 0.0))
+        return offs, hits[:int(offs[nq])], total
+
+    def search_weighted(self, query, threshold=0.0, num_results=0):
+        """one query -> [WeightedResult] in result order (doc_name, the weighted score, the total weight of the query in the
+        document's file)"""
+        _offs, hits, total = self.search_weighted_arrays([query], threshold, num_results)
+        return [WeightedResult(self.doc_name(f, d), sc, int(total[0, f])) for (f, d, sc) in hits.tolist()]
+
+    def position_weights(self, query):
+        """per file a uint8 array: the weight of every position of the query (host arithmetic over prevalence_arrays with
+        cobs_gpu_idf_weight)"""
+        offsets, counts = self.prevalence_arrays([query])
+        out = []
+        for f in range(self.num_files):
+            docs = int(self.info(f).num_docs)
+            seg = counts[int(offsets[f]):int(offsets[f + 1])]
+            out.append(np.array([self._lib.cobs_gpu_idf_weight(docs, int(c)) for c in seg], dtype=np.uint8))
+        return out
+
+    def weighted_ms(self):
+        """stage times of the weighted searches since the previous call of this method (HIP events, summed over passes)"""
+        t = (C.c_double * 5)()
+        check(self._lib.cobs_gpu_weighted_ms(self._h, C.byref(t)))
+        return {"hash_ms": t[0], "prevalence_ms": t[1], "weights_ms": t[2], "scan_ms": t[3], "passes": int(t[4])}
 
     # -- grouped search: which documents a SET of queries comes from -----------------
     GROUP_HIT_DTYPE = np.dtype([("file_no", "<u4"), ("doc", "<u4"), ("score", "<u4"), ("votes", "<u4")])

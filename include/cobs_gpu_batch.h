@@ -190,6 +190,42 @@ cobs_gpu_status cobs_gpu_doc_bits(cobs_gpu_index* ix, size_t file_no, uint64_t* 
 cobs_gpu_status cobs_gpu_prevalence(cobs_gpu_index* ix, const char* const* queries, const size_t* lens, size_t nq,
                                     uint32_t* counts, size_t cap, size_t* offsets, size_t* needed, size_t* bad_query);
 
+/* ---- IDF-weighted search ------------------------------------------------- */
+/* A search in which rare k-mers count for more, beyond the reference.  A plain score counts every position as 1; a k-mer
+ * that most of the collection holds then lifts every document over a threshold together.  Here, with c(q, f, p) exactly
+ * what cobs_gpu_prevalence returns (the real documents of file f in which terms p .. p + z of query q are all present,
+ * z the handle's findere) and D_f the real documents of file f, position p carries the weight
+ *   w = cobs_gpu_idf_weight(D_f, c):  0 when c = 0, else 1 + max{ j in 0..14 : c * 2^j <= D_f }
+ *                                     = 1 + min(14, floor(log2(D_f / c))), integer arithmetic only
+ * -- 0..15: a k-mer in more than half of the documents weighs 1, a singleton among >= 16384 documents 15 --, and
+ *   score(q, f, d) = the sum of w(q, f, p) over the positions p set in document d (real documents only),
+ *   W(q, f)        = the sum of w(q, f, p) over all n = T_f - z positions; total_weight[q * n_files + f] when not NULL.
+ * A position that no document holds carries no weight -- a sequencing error, or a window with a character outside ACGT
+ * under COBS_GPU_INVALID_MISS / _SKIP: the two policies give the SAME result here (a skipped position and a missed one
+ * both weigh 0 and W counts neither).  Under _ERROR an invalid base fails the call as it does for a search.
+ * For threshold > 0 a real document is a hit when score >= max(1, ceil(threshold * W(q, f))), computed in double; a
+ * (query, file) with W = 0 returns nothing.  For threshold <= 0 every real document is returned, score 0 included.
+ * Per query the records are ordered by score descending, then (file_no, doc) ascending, and cut to the first num_results
+ * when num_results > 0; the reference's "max_counts <= 1: index order" rule does NOT apply.  hits[hit_offsets[q] ..
+ * hit_offsets[q+1]) belong to query q, `score` is the weighted score.
+ * 15 * n must stay below 2^20 (the counter planes the scan is built for): a query with more than 69905 positions in some
+ * file fails with COBS_GPU_ERR_QUERY_TOO_LONG.
+ * Everything the host can refuse is refused before any device work: COBS_GPU_ERR_ARG (NULL arguments),
+ * COBS_GPU_ERR_QUERY_TOO_SHORT / _TOO_LONG (*bad_query = the offending query), COBS_GPU_ERR_UNSUPPORTED on a handle opened
+ * with an HBM budget (its rows are not all resident) or as one shard of several (the weights need every shard's counts).
+ * COBS_GPU_ERR_INVALID_BASE comes from the device (*bad_query).  COBS_GPU_ERR_CAPACITY when cap is too small --
+ * hit_offsets then holds the needed sizes (hit_offsets[nq] the total), known from the one scan that ran (hits may be NULL
+ * when cap is 0).  COBS_GPU_ERR_HIP when the device has no room for the hit records of a pass (hit_offsets stay 0: raise the
+ * threshold or pass fewer queries).  The device list (cobs_gpu_multi_*) has no counterpart.
+ * On the device: K1, the prevalence kernel into device cells, a kernel that turns the cells into one byte per position,
+ * W and the thresholds, and a scan shaped like K2 that adds a position's weight where K2 adds 1 and appends the documents
+ * that pass to a pool; no score matrix exists.  cobs_gpu_weighted_ms (cobs_gpu_diag.h) reads the stage timers. */
+uint32_t cobs_gpu_idf_weight(uint64_t num_docs, uint64_t count);      /* host arithmetic, no device */
+cobs_gpu_status cobs_gpu_search_weighted(cobs_gpu_index* ix, const char* const* queries, const size_t* lens, size_t nq,
+                                         double threshold, size_t num_results,
+                                         cobs_gpu_hit* hits, size_t cap, size_t* hit_offsets /* nq + 1 */,
+                                         uint64_t* total_weight /* optional, nq * n_files: W(q,f) */, size_t* bad_query);
+
 /* score slots per query held by THIS shard (== cobs_gpu_total_counts when
  * unsharded); device count rows have this many elements */
 uint64_t cobs_gpu_local_counts(const cobs_gpu_index* ix);

@@ -346,6 +346,38 @@ public:
         check(st);
     }
 
+    //! IDF-weighted search (beyond the reference; cobs_gpu_search_weighted): a position held by c of a file's D documents
+    //! weighs 1 + min(14, floor(log2(D / c))) (0 for c = 0), a document scores the sum of the weights of the positions it
+    //! holds and is a hit when that reaches max(1, ceil(threshold * W)); results[q] is ordered by score descending, then
+    //! (file, document).  total_weight (optional) receives W, [query][file].
+    void search_weighted(const std::vector<std::string>& queries, std::vector<std::vector<SearchResult>>& results,
+                         double threshold = 0.0, size_t num_results = 0,
+                         std::vector<std::vector<uint64_t>>* total_weight = nullptr) {
+        std::vector<const char*> qp;
+        std::vector<size_t> ql;
+        for (const auto& q : queries) { qp.push_back(q.data()); ql.push_back(q.size()); }
+        const size_t nq = queries.size(), nf = cobs_gpu_num_files(ix_);
+        std::vector<size_t> offs(nq + 1, 0);
+        std::vector<uint64_t> tw(nq * nf + 1, 0);
+        std::vector<cobs_gpu_hit> hits(16 * nq + 1024);
+        size_t bad = 0;
+        cobs_gpu_status st;
+        for (;;) {
+            st = cobs_gpu_search_weighted(ix_, qp.data(), ql.data(), nq, threshold, num_results, hits.data(), hits.size(),
+                                          offs.data(), tw.data(), &bad);
+            if (st != COBS_GPU_ERR_CAPACITY || offs[nq] <= hits.size()) break;
+            hits.resize(offs[nq]);          // (the call reported the needed size)
+        }
+        check(st);
+        results.assign(nq, {});
+        if (total_weight) total_weight->assign(nq, {});
+        for (size_t q = 0; q < nq; ++q) {
+            for (size_t i = offs[q]; i < offs[q + 1]; ++i)
+                results[q].push_back(SearchResult(cobs_gpu_doc_name(ix_, hits[i].file_no, hits[i].doc), hits[i].score));
+            if (total_weight) (*total_weight)[q].assign(tw.begin() + q * nf, tw.begin() + (q + 1) * nf);
+        }
+    }
+
     //! one document of a group's result: the sum of the scores of the group's queries and how many of them it was a hit of
     struct GroupResult {
         const char* doc_name;
