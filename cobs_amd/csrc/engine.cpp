@@ -76,6 +76,7 @@ Tuning Tuning::from_env() {
     if (const char* e = getenv("COBS_GPU_STREAM_PACKED")) t.stream_packed = atoi(e) != 0;
     if (const char* e = getenv("COBS_GPU_ROW_RANGE_MIN")) t.row_range_min = (uint32_t)std::max(1, atoi(e));
     if (const char* e = getenv("COBS_GPU_STREAM_BUF_KIB")) t.stream_buf_kib = (uint32_t)std::strtoul(e, nullptr, 0);
+    if (const char* e = getenv("COBS_GPU_IDX64")) t.idx64 = atoi(e) != 0;
     if (const char* e = getenv("COBS_GPU_EXP")) t.exp = (uint32_t)std::strtoul(e, nullptr, 0);      // A/B variants, also under the test suite
     return t;
 }
@@ -624,9 +625,7 @@ cobs_gpu_status cobs_gpu_set_findere(cobs_gpu_index* ix, uint32_t z) {
     if (z > 7u) return fail(COBS_GPU_ERR_ARG, "findere: z is 0 .. 7");
     if (z > 0u) {
         // a streamed file counts row ranges separately: no per-position presence to AND over the window
-        bool streamed = ix->hbm_budget != 0;
-        for (const Part& p : ix->parts) streamed = streamed || p.streamed;
-        if (streamed) return fail(COBS_GPU_ERR_UNSUPPORTED, "findere: not on a handle with an HBM budget (streamed files)");
+        if (ix->hbm_budget != 0 || any_streamed(ix)) return fail(COBS_GPU_ERR_UNSUPPORTED, "findere: not on a handle with an HBM budget (streamed files)");
     }
     ix->findere = z;
     return COBS_GPU_OK;

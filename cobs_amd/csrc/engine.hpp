@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <exception>
+#include <functional>
 #include <memory>
 #include <new>
 #include <string>
@@ -16,6 +17,7 @@
 #include "device_types.hpp"
 #include "index_file.hpp"
 #include "kernels.hpp"
+#include "row_table.hpp"
 
 namespace cobs_amd {
 
@@ -85,6 +87,37 @@ struct PinnedBuf {  // grow-only pinned host staging
     }
 };
 
+// N timing events around the N - 1 phases of a device pass, created on first use; add_elapsed books the phases' times.
+template <int N>
+struct PhaseEvents {
+    hipEvent_t ev[N] = {};
+    PhaseEvents() = default;
+    PhaseEvents(const PhaseEvents&) = delete;
+    PhaseEvents& operator=(const PhaseEvents&) = delete;
+    ~PhaseEvents() {
+        for (auto& e : ev) if (e) (void)hipEventDestroy(e);
+    }
+    hipError_t create() {
+        for (auto& e : ev)
+            if (!e)
+                if (hipError_t err = hipEventCreate(&e); err != hipSuccess) return err;
+        return hipSuccess;
+    }
+    hipError_t mark(int i, hipStream_t st) { return hipEventRecord(ev[i], st); }
+    // ms[i] += the time between events i and i + 1, for the phases [first, last) -- all of them or (an event cannot be
+    // read: the error is cleared) none; the events have completed
+    bool add_elapsed(double* ms, int first = 0, int last = N - 1) {
+        float t[N] = {};
+        for (int i = first; i < last; ++i)
+            if (hipEventElapsedTime(&t[i], ev[i], ev[i + 1]) != hipSuccess) {
+                (void)hipGetLastError();
+                return false;
+            }
+        for (int i = first; i < last; ++i) ms[i] += t[i];
+        return true;
+    }
+};
+
 // Tuning hooks.  The COBS_GPU_* environment variables are read ONCE, when an index is opened,
 // into the handle (never on the launch path); cobs_gpu_set_tuning changes them per handle
 // afterwards (the A/B scripts use that).  0 / -1 = automatic.
@@ -120,6 +153,7 @@ struct Tuning {
     uint32_t exp = 0;           // experimental kernel variants under A/B measurement (bit field, ScanArgs::exp)
     bool trace = false;         // COBS_GPU_TRACE: where the host side of a search call spends its time, on stderr
     uint32_t phase_slots = 0;   // tuning builds (make timing): work-groups of a scan launch that record phase stamps
+    bool idx64 = false;         // COBS_GPU_IDX64: every part keeps 64-bit row indices in K1's table (tests: the wide table on a small index)
     uint64_t hit_cap = 0;       // tests: at most this many records in a batch's hit pool (0 = its full capacity); lowers the
                                 // cap the kernels honour, never the allocation -- small fixtures reach the overflow paths
     static Tuning from_env();
@@ -449,6 +483,47 @@ uint64_t gathered_row_bytes(const Part& p);
 uint64_t pass_shape_class(const cobs_gpu_batch* b);
 void set_run_state(cobs_gpu_batch* b, double threshold, size_t topk, bool want_counts);
 void stage_thresholds(cobs_gpu_batch* b, double threshold);
+
+// ---- hash_pass.cpp: what the calls that run K1 share
+// ix->scratch[slot], created on first use with its stream and `done` event
+cobs_gpu_status scratch_batch(cobs_gpu_index* ix, int slot, cobs_gpu_batch** b = nullptr);
+// K1's arguments for file f of the batch's current queries, and its launch (the grid rounded up to 1024 threads)
+HashArgs hash_args_for(const cobs_gpu_batch* b, size_t f, const Part& p, size_t nq, uint32_t z, uint32_t invalid_bases, uint32_t* valid);
+cobs_gpu_status launch_hash_file(const cobs_gpu_batch* b, const HashArgs& ha, size_t nq, hipStream_t stream);
+// ... for every file the filter lets through, under the handle's invalid-bases policy, without valid-position counts
+cobs_gpu_status launch_hash_files(cobs_gpu_index* ix, const cobs_gpu_batch* b, size_t nq, uint32_t z, hipStream_t stream,
+                                  const std::function<bool(size_t)>& file_filter);
+// how a kernel finds K1's table of file f (row_table.hpp)
+TableRef table_ref_for(const cobs_gpu_batch* b, size_t f, const Part& p, uint32_t z);
+// K1's flag word (2^32-1 - first query of the pass with a non-ACGT character, 0 = none) -> OK, or ERR_INVALID_BASE with
+// the reference's message; *bad_query = base + that query, or map[that query]; n = queries of the pass
+std::string invalid_base_message(size_t query);
+cobs_gpu_status invalid_base_from_flags(uint32_t flag_word, size_t n, size_t* bad_query, size_t base = 0, const size_t* map = nullptr);
+// ERR_QUERY_TOO_SHORT with the reference's wording
+cobs_gpu_status query_too_short(uint64_t need, uint32_t z, size_t query);
+// the refusals of a second-call feature, query by query and before anything is launched: NULL query, shorter than the
+// longest term + z, then the feature's own rule(q) (too long, its hits, ...); *bad_query = the query looked at, 0 after
+// the last; skip(q) (may be empty): a query the call does not look at
+cobs_gpu_status check_query_lengths(const cobs_gpu_index* ix, const char* const* queries, const size_t* lens, size_t nq, uint32_t z,
+                                    const std::function<cobs_gpu_status(size_t)>& rule, size_t* bad_query,
+                                    const std::function<bool(size_t)>& skip = nullptr);
+// bytes of K1's tables per query character, all files: what the calls cut their device passes by
+uint64_t table_bytes_per_char(const cobs_gpu_index* ix);
+bool any_streamed(const cobs_gpu_index* ix);
+// fn(chunk) -> status for every chunk of the part that is resident and holds pages
+template <typename F>
+cobs_gpu_status for_each_resident_chunk(const Part& p, F&& fn) {
+    for (const Chunk& ch : p.chunks) {
+        if (!ch.d_data || ch.pages.empty()) continue;
+        if (cobs_gpu_status s = fn(ch); s != COBS_GPU_OK) return s;
+    }
+    return COBS_GPU_OK;
+}
+// the prevalence of the batch's n queries into `cells` (segment (q, f) at seg_off[q * files + f]): cells zeroed |
+// `started` | K1 on every file | `hashed` | the prevalence kernel over every resident chunk
+cobs_gpu_status launch_prevalence_cells(cobs_gpu_index* ix, const cobs_gpu_batch* b, const uint64_t* seg_off, uint32_t* cells,
+                                        uint64_t ncells, size_t n, size_t max_len, uint32_t z, hipStream_t stream,
+                                        hipEvent_t started, hipEvent_t hashed);
 
 // ---- results.cpp
 // `n` hit records at d_pool (the batch's own pool, or the pools of all shards after an exchange) -> b->h_hits in result

@@ -33,6 +33,7 @@
 
 #include "device_types.hpp"
 #include "kernels.hpp"
+#include "row_table.hpp"     // K1's row-index table, read here entry by entry
 
 namespace cobs_amd {
 
@@ -69,7 +70,7 @@ __device__ __forceinline__ uint32_t query_of_entry(const uint64_t* blk_off, uint
     uint32_t lo = 0, hi = nq;
     while (hi - lo > 1u) {
         const uint32_t mid = (lo + hi) >> 1;
-        if ((blk_off[mid] + mid) * per <= n) lo = mid; else hi = mid;
+        if (row_table_query_first(blk_off[mid], mid, per) <= n) lo = mid; else hi = mid;
     }
     return lo;
 }
@@ -85,17 +86,17 @@ __global__ __launch_bounds__(256) void count_rows_kernel(CountArgs a, uint64_t t
         for (uint32_t i = threadIdx.x; i < a.ncounters; i += 256u) h[i] = 0u;
         __syncthreads();
     }
-    const uint64_t per = 8ull * a.num_hashes;
+    const uint64_t per = row_table_per(a.num_hashes);
     for (uint64_t g = (uint64_t)blockIdx.x * 256u + threadIdx.x; g < total; g += (uint64_t)gridDim.x * 256u) {
         // entry g of the whole table: [query][sub-index][block + padding block][hash][8]
-        const uint64_t perq = per * a.table_npages;
+        const uint64_t perq = row_table_per_all(a.num_hashes, a.table_npages);
         uint32_t lo = 0, hi = a.nq;
         while (hi - lo > 1u) {
             const uint32_t mid = (lo + hi) >> 1;
-            if ((a.blk_off[mid] + mid) * perq <= g) lo = mid; else hi = mid;
+            if (row_table_query_first(a.blk_off[mid], mid, perq) <= g) lo = mid; else hi = mid;
         }
         const uint64_t nblk1 = a.blk_off[lo + 1] - a.blk_off[lo] + 1u;
-        const uint64_t within = g - (a.blk_off[lo] + lo) * perq;
+        const uint64_t within = g - row_table_query_first(a.blk_off[lo], lo, perq);
         const uint32_t p = (uint32_t)(within / (nblk1 * per));
         const CountPage cp = a.cpages[p];
         if (cp.first == 0xFFFFFFFFu) continue;
@@ -130,11 +131,11 @@ __global__ __launch_bounds__(256) void count_rows_kernel(CountArgs a, uint64_t t
 //   list    the source row of every slot, from the bitmap: ascending -- the copy sweeps the file front to back
 template <typename IdxT>
 __device__ __forceinline__ bool gather_entry(const GatherArgs& a, const GatherPage& pg, uint64_t n, uint64_t* e, uint64_t* r) {
-    const uint64_t per = 8ull * a.num_hashes;
+    const uint64_t per = row_table_per(a.num_hashes);
     const uint32_t q = query_of_entry(a.blk_off, a.nq, per, n);
     const uint64_t b0 = a.blk_off[q];
     const uint64_t nblk1 = a.blk_off[q + 1] - b0 + 1u;
-    *e = ((b0 + q) * a.table_npages + (uint64_t)pg.tpage * nblk1) * per + (n - (b0 + q) * per);
+    *e = row_table_first(b0, q, a.table_npages, pg.tpage, nblk1, per) + (n - row_table_query_first(b0, q, per));
     // (a row outside the page's range -- and K1's padding row S_p, which lies beyond every range -- is not gathered:
     // its entry names the page's zero row)
     *r = (uint64_t)reinterpret_cast<const IdxT*>(a.table)[*e] - pg.row0;
@@ -283,15 +284,15 @@ template <typename IdxT>
 __global__ __launch_bounds__(256) void remap_rows_kernel(RemapArgs a, uint64_t entries) {
     const uint64_t n = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (n >= entries) return;
-    const uint64_t per = 8ull * a.num_hashes;
+    const uint64_t per = row_table_per(a.num_hashes);
     uint32_t lo = 0, hi = a.nq;                            // query of entry n: the last q with (blk_off[q] + q) * per <= n
     while (hi - lo > 1u) {
         const uint32_t mid = (lo + hi) >> 1;
-        if ((a.blk_off[mid] + mid) * per <= n) lo = mid; else hi = mid;
+        if (row_table_query_first(a.blk_off[mid], mid, per) <= n) lo = mid; else hi = mid;
     }
     const uint64_t b0 = a.blk_off[lo];
     const uint64_t nblk1 = a.blk_off[lo + 1] - b0 + 1u;
-    const uint64_t e = ((b0 + lo) * a.table_npages + (uint64_t)a.tpage * nblk1) * per + (n - (b0 + lo) * per);
+    const uint64_t e = row_table_first(b0, lo, a.table_npages, a.tpage, nblk1, per) + (n - row_table_query_first(b0, lo, per));
     const uint64_t r = (uint64_t)reinterpret_cast<const IdxT*>(a.table)[e] - a.row0;
     reinterpret_cast<IdxT*>(a.table2)[e] = (IdxT)(r < a.nrows ? r : a.nrows);
 }
@@ -300,9 +301,9 @@ __global__ __launch_bounds__(256) void remap_rows_kernel(RemapArgs a, uint64_t e
 // one wave per query: how many entries of its sub-index `tpage` name a row of the unit
 __global__ __launch_bounds__(64) void compact_count_kernel(CompactArgs a) {
     const uint32_t q = blockIdx.x, lane = threadIdx.x;
-    const uint64_t b0 = a.blk_off[q];
-    const uint32_t nblk = (uint32_t)(a.blk_off[q + 1] - b0);
-    const uint32_t* t = a.table2 + ((b0 + q) * a.table_npages + (uint64_t)a.tpage * (nblk + 1u)) * 8ull;
+    const RowTable<uint32_t> rt(a.table2, a.blk_off, a.table_npages, q, a.tpage, 1u);      // (one hash function)
+    const uint32_t nblk = rt.nblk;
+    const uint32_t* t = rt.base;
     uint32_t n = 0;
     for (uint32_t i = lane; i < nblk * 8u; i += 64u) n += t[i] != a.zero_idx ? 1u : 0u;
 #pragma unroll
@@ -338,12 +339,12 @@ __global__ __launch_bounds__(1024) void compact_scan_kernel(CompactArgs a) {
 // block) point at the zero row
 __global__ __launch_bounds__(64) void compact_write_kernel(CompactArgs a) {
     const uint32_t q = blockIdx.x, lane = threadIdx.x;
-    const uint64_t b0 = a.blk_off[q];
-    const uint32_t nblk = (uint32_t)(a.blk_off[q + 1] - b0);
-    const uint32_t* t = a.table2 + ((b0 + q) * a.table_npages + (uint64_t)a.tpage * (nblk + 1u)) * 8ull;
+    const RowTable<uint32_t> rt(a.table2, a.blk_off, a.table_npages, q, a.tpage, 1u);      // (one hash function)
+    const uint32_t nblk = rt.nblk;
+    const uint32_t* t = rt.base;
     const uint64_t c0 = a.blk2[q];
     const uint32_t nb2 = (uint32_t)(a.blk2[q + 1] - c0);
-    uint32_t* o = a.table3 + ((c0 + q) * a.table_npages + (uint64_t)a.tpage * (nb2 + 1u)) * 8ull;
+    uint32_t* o = a.table3 + row_table_first(c0, q, a.table_npages, a.tpage, nb2 + 1u, row_table_per(1u));
     uint32_t off = 0;
     for (uint32_t i0 = 0; i0 < nblk * 8u; i0 += 64u) {
         const uint32_t i = i0 + lane;

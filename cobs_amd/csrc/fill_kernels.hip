@@ -21,20 +21,13 @@
 #include <algorithm>
 
 #include "fill_kernels.hpp"
+#include "wave_ops.hpp"      // csa
 
 namespace cobs_amd {
 
 namespace {
 
 constexpr int NP = kFillPlanes;
-
-// carry-save adder: (h, l) = a + b + c per bit position (v_bitop3_b32: majority 0xE8, parity 0x96)
-__device__ __forceinline__ void csa(uint32_t& h, uint32_t& l, uint32_t a, uint32_t b, uint32_t c) {
-    const uint32_t hh = __builtin_amdgcn_bitop3_b32(a, b, c, 0xE8);
-    const uint32_t ll = __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
-    h = hh;
-    l = ll;
-}
 
 // eight row words into the planes of one column word
 __device__ __forceinline__ void absorb8(uint32_t (&pl)[NP], uint32_t x0, uint32_t x1, uint32_t x2, uint32_t x3, uint32_t x4,

@@ -158,12 +158,7 @@ cobs_gpu_status pass_end(const Call& c, const Pass& ps) {
     else (void)hipGetLastError();
     const uint32_t* land = w->h_land[ps.slot].p;
     const size_t n = ps.g1 - ps.g0, nf = ix->parts.size();
-    if (land[0] != 0u) {                 // K1 keeps 2^32-1 - (first query with a non-ACGT character)
-        const size_t bad = ps.g0 + std::min<size_t>(0xFFFFFFFFu - land[0], n - 1);
-        if (c.bad_query) *c.bad_query = bad;
-        return fail(COBS_GPU_ERR_INVALID_BASE, "Invalid DNA base pair in query string. Only ACGT are allowed. (query " +
-                                               std::to_string(bad) + ")");
-    }
+    if (cobs_gpu_status s = invalid_base_from_flags(land[0], n, c.bad_query, ps.g0); s != COBS_GPU_OK) return s;
     if (c.count_valid) {
         size_t g = ps.group0;
         for (size_t q = ps.g0; q < ps.g1; ++q) {
@@ -187,26 +182,17 @@ cobs_gpu_status search_groups_impl(cobs_gpu_index* ix, const char* const* querie
             return fail(COBS_GPU_ERR_ARG, "group_offsets are not ascending (group " + std::to_string(g) + ")");
     if (group_offsets[n_groups] != nq) return fail(COBS_GPU_ERR_ARG, "group_offsets[n_groups] is not the number of queries");
     if (n_groups >= 0xFFFFFFF0ull || nq >= 0xFFFFFFF0ull) return fail(COBS_GPU_ERR_ARG, "too many groups or queries");
-    bool streamed = ix->hbm_budget != 0;
-    for (const Part& p : ix->parts) streamed = streamed || p.streamed;
-    if (streamed) return fail(COBS_GPU_ERR_UNSUPPORTED, "groups: not on a handle with an HBM budget (its score rows are added up range by range)");
+    if (ix->hbm_budget != 0 || any_streamed(ix)) return fail(COBS_GPU_ERR_UNSUPPORTED, "groups: not on a handle with an HBM budget (its score rows are added up range by range)");
     if (ix->shard_count > 1) return fail(COBS_GPU_ERR_UNSUPPORTED, "groups: not on one shard of several (a group's totals are per shard)");
     for (size_t g = 0; g <= n_groups; ++g) hit_offsets[g] = 0;
     const size_t nf = ix->parts.size();
     const uint32_t z = ix->findere;
-    uint32_t max_term = 0;
-    for (const Part& p : ix->parts) max_term = std::max(max_term, p.meta.term_size);
     // everything the host can refuse is refused before anything is launched
-    for (size_t q = 0; q < nq; ++q) {
-        if (bad_query) *bad_query = q;
-        if (!queries[q]) return fail(COBS_GPU_ERR_ARG, "NULL query (query " + std::to_string(q) + ")");
-        if (lens[q] < (size_t)max_term + z)
-            return fail(COBS_GPU_ERR_QUERY_TOO_SHORT, "query too short, needs to be at least " + std::to_string(max_term + z) +
-                        " characters long" + (z ? " with findere z = " + std::to_string(z) : std::string()) +
-                        " (query " + std::to_string(q) + ")");
+    cobs_gpu_status refused = check_query_lengths(ix, queries, lens, nq, z, [&](size_t q) -> cobs_gpu_status {
         if (lens[q] >= 0xFFFFFFF0ull) return fail(COBS_GPU_ERR_QUERY_TOO_LONG, "query too long (query " + std::to_string(q) + ")");
-    }
-    if (bad_query) *bad_query = 0;
+        return COBS_GPU_OK;
+    }, bad_query);
+    if (refused != COBS_GPU_OK) return refused;
     // P: the positions every group is scored over per file -- T - z summed (the nominal count, which also bounds a sum:
     // they are 32-bit), or under `skip` the valid positions K1 counts
     std::vector<uint64_t> pos(n_groups * nf, 0);
@@ -246,8 +232,7 @@ cobs_gpu_status search_groups_impl(cobs_gpu_index* ix, const char* const* querie
     const uint64_t kLimit = ix->tune.pass_bytes;
     uint32_t min_term = 0xFFFFFFFFu;
     for (const Part& p : ix->parts) min_term = std::min(min_term, p.meta.term_size);
-    uint64_t terms_per_char = 0;
-    for (const Part& p : ix->parts) terms_per_char += 4ull * p.meta.num_hashes * std::max<uint32_t>(p.num_tpages(), 1) * (p.idx64 ? 2 : 1);
+    const uint64_t terms_per_char = table_bytes_per_char(ix);
     auto score_bytes = [&](uint64_t max_len) -> uint64_t {
         const uint64_t terms = max_len - min_term + 1;
         return std::max<uint64_t>(terms <= 255 ? 1 : terms <= 65535 ? 2 : 4, ix->tune.min_score_bytes);

@@ -33,13 +33,8 @@ static cobs_gpu_status host_pass_begin(cobs_gpu_index* ix, int slot, const char*
                                        size_t nq, double threshold, size_t topk, hipEvent_t after,
                                        size_t* bad_at = nullptr, size_t index_base = 0) {
     HIP_TRY(hipSetDevice(ix->device));
-    if (!ix->scratch[slot]) {
-        cobs_gpu_status st = cobs_gpu_batch_create(ix, 0, 0, &ix->scratch[slot]);
-        if (st != COBS_GPU_OK) return st;
-        HIP_TRY(hipStreamCreateWithFlags(&ix->scratch[slot]->own_stream, hipStreamNonBlocking));
-        HIP_TRY(hipEventCreateWithFlags(&ix->scratch[slot]->done, hipEventDisableTiming));
-    }
-    cobs_gpu_batch* b = ix->scratch[slot];
+    cobs_gpu_batch* b = nullptr;
+    if (cobs_gpu_status cs = scratch_batch(ix, slot, &b); cs != COBS_GPU_OK) return cs;
     b->flags_landing = false;
     ix->host_passes++;
     double t0 = now_s();
@@ -233,11 +228,7 @@ static cobs_gpu_status host_pass_end(cobs_gpu_index* ix, int slot, double thresh
         b->synced = true;
         st = fetch_valid(b);
         if (st != COBS_GPU_OK) return st;
-        if (b->h_flags[0] != 0u) {           // K1 keeps 2^32-1 - (first query with a non-ACGT character)
-            if (bad_query) *bad_query = 0xFFFFFFFFu - b->h_flags[0];
-            st = fail(COBS_GPU_ERR_INVALID_BASE, "Invalid DNA base pair in query string. Only ACGT are allowed. (query " +
-                                                 std::to_string(0xFFFFFFFFu - b->h_flags[0]) + ")");
-        }
+        st = invalid_base_from_flags(b->h_flags[0], b->nq, bad_query);
     } else {
         st = cobs_gpu_batch_sync(b, b->own_stream, bad_query);
     }
@@ -286,14 +277,12 @@ static cobs_gpu_status search_batch_impl(cobs_gpu_index* ix, const char* const* 
     const uint64_t kLimit = ix->tune.pass_bytes;
     uint32_t min_term = 0xFFFFFFFFu;
     for (const auto& p : ix->parts) min_term = std::min(min_term, p.meta.term_size);
-    uint64_t terms_per_char = 0;                      // table bytes per query character, all files
-    for (const auto& p : ix->parts) terms_per_char += 4ull * p.meta.num_hashes * std::max<uint32_t>(p.num_tpages(), 1) * (p.idx64 ? 2 : 1);
+    const uint64_t terms_per_char = table_bytes_per_char(ix);      // table bytes per query character, all files
     // Passes are pipelined over up to three scratch batches: while the GPU scans pass i the host
     // stages and uploads pass i+1 and ranks pass i-1 (kernels of consecutive passes are chained by
     // events, so they never share the GPU).  A call with 4 MiB of query text or more is cut into at
     // least four passes for that.  Streamed (out-of-core) files share their chunk buffers: one pass at a time.
-    bool any_streamed = false;
-    for (const auto& p : ix->parts) any_streamed = any_streamed || p.streamed;
+    const bool any_streamed = cobs_amd::any_streamed(ix);
     const size_t depth = any_streamed ? 1 : (size_t)cobs_gpu_index::kScratch;
     uint64_t total_chars = 0;
     for (size_t q = 0; q < nq; ++q) total_chars += lens[q];
@@ -341,8 +330,7 @@ static cobs_gpu_status search_batch_impl(cobs_gpu_index* ix, const char* const* 
         if (st != COBS_GPU_OK) {
             if (bad_query) *bad_query = ps.g0 + bad;
             if (st == COBS_GPU_ERR_INVALID_BASE)          // the message names the query by its index in the call
-                return fail(st, "Invalid DNA base pair in query string. Only ACGT are allowed. (query " +
-                                std::to_string(ps.g0 + bad) + ")");
+                return fail(st, invalid_base_message(ps.g0 + bad));
             return st;
         }
         cobs_gpu_batch* sb = ix->scratch[ps.slot];

@@ -29,7 +29,9 @@
 
 #include "device_types.hpp"
 #include "kernels.hpp"
+#include "row_table.hpp"     // K1's row-index table: the writer below, K2's reader
 #include "term_hash.hpp"     // rotl64 .. xxh64_view, comp4 / xxh64_31 / canon31, all_acgt / has_newline / set_term_bit
+#include "wave_ops.hpp"      // dpp_mov and its control constants, csa
 
 namespace cobs_amd {
 
@@ -109,7 +111,7 @@ __global__ __launch_bounds__(256) void hash_kernel(HashArgs a, uint64_t total_th
     if (i >= tblk * 8u) return;
     const uint32_t H = a.num_hashes;
     const uint32_t blk = i >> 3, sub = i & 7u;
-    IdxT* out = reinterpret_cast<IdxT*>(a.table) + ((b0 + q) * a.npages) * (8ull * H);
+    const RowTableWriter<IdxT> tab(a.table, b0, q, a.npages, H, tblk);
 
     bool term_ok = true;
     if (lenient) {
@@ -124,8 +126,7 @@ __global__ __launch_bounds__(256) void hash_kernel(HashArgs a, uint64_t total_th
     if (i >= T || !term_ok) {       // padding term (or one that holds an invalid character): the all-zero row of every sub-index
         for (uint32_t p = 0; p < a.npages; ++p) {
             const IdxT zr = (IdxT)a.pages[p].sig;
-            IdxT* o = out + ((uint64_t)p * tblk + blk) * (8ull * H) + sub;
-            for (uint32_t j = 0; j < H; ++j) o[j * 8] = zr;
+            for (uint32_t j = 0; j < H; ++j) tab.out(p, blk, j, sub) = zr;
         }
         return;
     }
@@ -148,7 +149,7 @@ __global__ __launch_bounds__(256) void hash_kernel(HashArgs a, uint64_t total_th
         const uint64_t h = xxh64_view(kv, (uint64_t)j);
         for (uint32_t p = 0; p < a.npages; ++p) {
             const PageDev pg = a.pages[p];
-            out[((uint64_t)p * tblk + blk) * (8ull * H) + j * 8 + sub] = (IdxT)fast_mod(h, pg.sig, pg.magic);
+            tab.out(p, blk, j, sub) = (IdxT)fast_mod(h, pg.sig, pg.magic);
         }
     }
 }
@@ -182,7 +183,7 @@ __global__ __launch_bounds__(256) void hash_kernel_k31(HashArgs a, uint64_t tota
     if (i >= tblk * 8u) return;
     const uint32_t H = a.num_hashes;
     const uint32_t blk = i >> 3, sub = i & 7u;
-    IdxT* out = reinterpret_cast<IdxT*>(a.table) + ((b0 + q) * a.npages) * (8ull * H);
+    const RowTableWriter<IdxT> tab(a.table, b0, q, a.npages, H, tblk);
     // the k-mer and one following byte as 8 (unaligned) dwords; the text buffer is padded
     uint32_t f[8];
     if (i < T) {
@@ -211,8 +212,7 @@ __global__ __launch_bounds__(256) void hash_kernel_k31(HashArgs a, uint64_t tota
     if (i >= T || !term_ok) {
         for (uint32_t p = 0; p < a.npages; ++p) {
             const IdxT zr = (IdxT)a.pages[p].sig;
-            IdxT* o = out + ((uint64_t)p * tblk + blk) * (8ull * H) + sub;
-            for (uint32_t j = 0; j < H; ++j) o[j * 8] = zr;
+            for (uint32_t j = 0; j < H; ++j) tab.out(p, blk, j, sub) = zr;
         }
         return;
     }
@@ -224,7 +224,7 @@ __global__ __launch_bounds__(256) void hash_kernel_k31(HashArgs a, uint64_t tota
         const uint64_t h = xxh64_31(c, (uint64_t)j);
         for (uint32_t p = 0; p < a.npages; ++p) {
             const PageDev pg = a.pages[p];
-            out[((uint64_t)p * tblk + blk) * (8ull * H) + j * 8 + sub] = (IdxT)fast_mod(h, pg.sig, pg.magic);
+            tab.out(p, blk, j, sub) = (IdxT)fast_mod(h, pg.sig, pg.magic);
         }
     }
 }
@@ -237,15 +237,7 @@ __global__ __launch_bounds__(256) void hash_kernel_k31(HashArgs a, uint64_t tota
 // their partial plane counters (shuffles inside a wave, LDS across waves) at the
 // end.  A lane owns one chunk: 128 documents, held as 4 column words x NP bit planes.
 
-// carry-save adder: (h, l) = a + b + c per bit position.  gfx950 has a
-// three-input boolean op (v_bitop3_b32, 8-bit truth table), so majority (0xE8)
-// and parity (0x96) are one instruction each: a CSA is 2 VALU ops.
-__device__ __forceinline__ void csa(uint32_t& h, uint32_t& l, uint32_t a, uint32_t b, uint32_t c) {
-    const uint32_t hh = __builtin_amdgcn_bitop3_b32(a, b, c, 0xE8);
-    const uint32_t ll = __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
-    h = hh;
-    l = ll;
-}
+// (the carry-save adder csa -- two v_bitop3_b32 -- is in wave_ops.hpp)
 
 // fold eight gathered row words into planes 0..2 of one column word; returns the
 // carry into plane 3 ("eights")
@@ -523,19 +515,7 @@ __device__ __forceinline__ void planes_to_bytes32(const uint32_t (&P)[NP], uint3
 // 128 bytes of scores + 16 of padding, so that the 16-byte writes of 16 lanes hit 16 different banks
 constexpr uint32_t kStageStride = 144u;
 
-// Cross-lane steps inside a row of 16 lanes as DPP modifiers of the VALU (v_add_u32 ..._dpp: no trip through the
-// LDS crossbar, which a ds_bpermute-based __shfl costs -- ~100 cycles of latency per dependent step).
-template <int CTRL, int ROW_MASK = 0xF, int BANK_MASK = 0xF, bool BOUND_ZERO = true>
-__device__ __forceinline__ uint32_t dpp_mov(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, BANK_MASK, BOUND_ZERO);
-}
-constexpr int kDppQuadXor1 = 0xB1;       // quad_perm:[1,0,3,2]
-constexpr int kDppQuadXor2 = 0x4E;       // quad_perm:[2,3,0,1]
-constexpr int kDppRowMirror = 0x140;     // lane i <- lane 15 - i of its row
-constexpr int kDppHalfMirror = 0x141;    // lane i <- lane 7 - i of its half row
-constexpr int kDppRowShr = 0x110;        // + n: lane i <- lane i - n of its row (0 shifted in)
-constexpr int kDppBcast15 = 0x142;       // lane 15 of a row -> every lane of the next row
-constexpr int kDppBcast31 = 0x143;       // lane 31 -> every lane of rows 2 and 3
+// (cross-lane steps as DPP modifiers of the VALU: dpp_mov and its control constants, wave_ops.hpp)
 
 // sum of `c` over the W (power of two, 4..64) consecutive lanes of a lane group, in every lane of the group
 __device__ __forceinline__ uint32_t group_allsum(uint32_t c, uint32_t W) {
@@ -753,13 +733,14 @@ __global__ __launch_bounds__(NW * 64, (!FZ && ((TK && H1) || (!H1 && sizeof(IdxT
         tmeta[col * 3 + 2] = pdl.doc0 + ch * 128u;
     }
 
-    const uint64_t b0 = a.blk_off[q];
-    const uint32_t nblk_q = (uint32_t)(a.blk_off[q + 1] - b0);   // table stride of query q
-    const uint32_t nblk = qlive ? nblk_q : 0u;
     const uint32_t H = H1 ? 1u : a.num_hashes;
-    // row indices of this lane's sub-index: [nblk + 1 blocks][hash][8]; block nblk is all padding
-    const IdxT* tab = reinterpret_cast<const IdxT*>(a.table) +
-                      ((b0 + q) * a.table_npages + (uint64_t)pdl.tpage * (nblk_q + 1u)) * (8ull * H);
+    // row indices of this lane's sub-index (row_table.hpp): [nblk + 1 blocks][hash][8]; block nblk is all padding
+    const RowTable<IdxT> rt(a.table, a.blk_off, a.table_npages, q, pdl.tpage, H);
+    const uint32_t nblk_q = rt.nblk;                             // table stride of query q
+    const uint32_t nblk = qlive ? nblk_q : 0u;
+    // (the loops below walk blocks from this pointer with their own offsets, b * 8 * H: rt.block(b), spelled out where
+    // the software-pipelined loads take raw addresses)
+    const IdxT* tab = rt.base;
     const uint32_t vw = MQ ? wave : wave * G + grp;  // virtual wave of this lane
     const uint32_t NV = MQ ? (uint32_t)NW : NW * G;
     // findere: blocks [fz_first, fz_first + fz_per) of the query (a sliding window needs its terms in order)

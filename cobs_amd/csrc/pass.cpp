@@ -48,9 +48,7 @@ cobs_gpu_status check_findere_lengths(const cobs_gpu_batch* b, size_t index_base
     for (const Part& p : b->ix->parts) max_term = std::max(max_term, p.meta.term_size);
     for (size_t q = 0; q < b->nq; ++q)
         if ((uint64_t)b->lens[q] < (uint64_t)max_term + b->findere)
-            return fail(COBS_GPU_ERR_QUERY_TOO_SHORT, "query too short, needs to be at least " +
-                        std::to_string(max_term + b->findere) + " characters long with findere z = " +
-                        std::to_string(b->findere) + " (query " + std::to_string(index_base + q) + ")");
+            return query_too_short((uint64_t)max_term + b->findere, b->findere, index_base + q);
     return COBS_GPU_OK;
 }
 
@@ -139,10 +137,7 @@ cobs_gpu_status cobs_amd::set_queries_on(cobs_gpu_batch* b, const char* const* q
         if (bad_query) *bad_query = q;
         if (!queries[q]) return fail(COBS_GPU_ERR_ARG, "NULL query (query " + std::to_string(index_base + q) + ")");
         if (lens[q] < max_term + ix->findere)
-            return fail(COBS_GPU_ERR_QUERY_TOO_SHORT, "query too short, needs to be at least " +
-                        std::to_string(max_term + ix->findere) + " characters long" +
-                        (ix->findere ? " with findere z = " + std::to_string(ix->findere) : std::string()) +
-                        " (query " + std::to_string(index_base + q) + ")");
+            return query_too_short((uint64_t)max_term + ix->findere, ix->findere, index_base + q);
         if (lens[q] - max_term >= 0xFFFFFFFFull || lens[q] >= 0xFFFFFFF0ull)
             return fail(COBS_GPU_ERR_QUERY_TOO_LONG, "query too long (query " + std::to_string(index_base + q) + ")");
         max_terms = std::max<uint64_t>(max_terms, lens[q] - min_term + 1);
@@ -413,26 +408,8 @@ cobs_gpu_status cobs_amd::run_impl(cobs_gpu_batch* b, double threshold, size_t t
     for (size_t f = 0; f < ix->parts.size(); ++f) {
         Part& p = ix->parts[f];
         if (nq == 0 || p.chunks.empty()) continue;
-        HashArgs ha;
-        ha.text = b->d_text;
-        ha.span_off = b->d_span_off;
-        ha.q_len = b->d_qlen;
-        ha.blk_off = b->work[f].blk_off;
-        ha.pages = p.d_tpages;
-        ha.table = b->work[f].table.p;
-        ha.err_query = b->flags.p;
-        ha.nq = (uint32_t)nq;
-        ha.npages = p.num_tpages();
-        ha.term_size = p.meta.term_size;
-        ha.canonicalize = p.meta.canonicalize;
-        ha.num_hashes = (uint32_t)p.meta.num_hashes;
-        ha.idx64 = p.idx64 ? 1u : 0u;
-        ha.invalid_bases = b->invalid_bases;
-        ha.findere = b->findere;
-        ha.valid = count_valid ? b->valid.p + f * nq : nullptr;
-        // (the kernel bounds itself by span_off[nq] on the device; the grid is rounded up so that a
-        // captured launch serves every batch of its shape class)
-        HIP_TRY(launch_hash(ha, round_up(b->span_off[nq], 1024), hs));
+        const HashArgs k1 = hash_args_for(b, f, p, nq, b->findere, b->invalid_bases, count_valid ? b->valid.p + f * nq : nullptr);
+        if (cobs_gpu_status s = launch_hash_file(b, k1, nq, hs); s != COBS_GPU_OK) return s;
         if (skip_thr) {
             SkipThresholdArgs ta;
             if (p.meta.canonicalize != 0) {
@@ -1024,14 +1001,7 @@ cobs_gpu_status cobs_gpu_batch_sync(cobs_gpu_batch* b, void* hip_stream, size_t*
     }
     b->synced = true;
     if (cobs_gpu_status vs = fetch_valid(b); vs != COBS_GPU_OK) return vs;
-    if (b->h_flags[0] != 0u) {           // K1 keeps 2^32-1 - (first query with a non-ACGT character)
-        const uint32_t bad = 0xFFFFFFFFu - b->h_flags[0];
-        if (bad_query) *bad_query = bad;
-        return fail(COBS_GPU_ERR_INVALID_BASE,
-                    "Invalid DNA base pair in query string. Only ACGT are allowed. (query " +
-                    std::to_string(bad) + ")");
-    }
-    return COBS_GPU_OK;
+    return invalid_base_from_flags(b->h_flags[0], b->nq, bad_query);
 }
 
 

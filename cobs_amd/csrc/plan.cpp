@@ -295,7 +295,8 @@ cobs_gpu_status plan_part(Part& pt, const cobs_gpu_index* ix) {
     cobs_gpu_status st = check_meta(m);
     if (st != COBS_GPU_OK) return st;
     // row indices are 32-bit unless a sub-index (plus its zero row) does not fit them
-    pt.idx64 = false;
+    // (COBS_GPU_IDX64: the wide table on request, so that a small index exercises it)
+    pt.idx64 = ix->tune.idx64;
     for (uint64_t s : m.signature_sizes)
         if (s >= 0xFFFFFFFFull) pt.idx64 = true;
     const uint64_t prb = m.page_row_bytes();

@@ -19,12 +19,9 @@ struct PositionsWork {
     DevBuf<PresencePair> pairs;
     DevBuf<uint64_t> bits;
     PinnedBuf<uint32_t> h_flags;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};      // before K1 | after K1 | after the presence kernels
-    double presence_ms = 0, hash_ms = 0;
+    PhaseEvents<3> ev;          // before K1 | after K1 | after the presence kernels
+    double ms[2] = {0, 0};      // hash | presence
     uint64_t passes = 0;
-    ~PositionsWork() {
-        for (auto& e : ev) if (e) (void)hipEventDestroy(e);
-    }
 };
 
 void destroy_positions_work(PositionsWork* w) { delete w; }
@@ -67,14 +64,9 @@ cobs_gpu_status run_pass(const Call& c, const std::vector<size_t>& qsel) {
     HIP_TRY(hipSetDevice(ix->device));
     if (!ix->positions) ix->positions = new PositionsWork;
     PositionsWork* w = ix->positions;
-    for (auto& e : w->ev) if (!e) HIP_TRY(hipEventCreate(&e));
-    if (!ix->scratch[0]) {          // the workspace of the host-buffer calls (host_api.cpp): query upload and K1's tables
-        cobs_gpu_status st = cobs_gpu_batch_create(ix, 0, 0, &ix->scratch[0]);
-        if (st != COBS_GPU_OK) return st;
-        HIP_TRY(hipStreamCreateWithFlags(&ix->scratch[0]->own_stream, hipStreamNonBlocking));
-        HIP_TRY(hipEventCreateWithFlags(&ix->scratch[0]->done, hipEventDisableTiming));
-    }
-    cobs_gpu_batch* b = ix->scratch[0];
+    HIP_TRY(w->ev.create());
+    cobs_gpu_batch* b = nullptr;
+    if (cobs_gpu_status s = scratch_batch(ix, 0, &b); s != COBS_GPU_OK) return s;
     hipStream_t st = b->own_stream;
     const size_t n = qsel.size();
     std::vector<const char*> qp(n);
@@ -113,66 +105,26 @@ cobs_gpu_status run_pass(const Call& c, const std::vector<size_t>& qsel) {
     HIP_TRY(w->h_flags.reserve(4));
     HIP_TRY(hipMemcpyAsync(w->pairs.p, pairs.data(), pairs.size() * sizeof(PresencePair), hipMemcpyHostToDevice, st));
     HIP_TRY(launch_clear_flags(b->flags.p, st));
-    HIP_TRY(hipEventRecord(w->ev[0], st));
+    HIP_TRY(w->ev.mark(0, st));
+    // (K1 once per file that has pairs)
+    if (cobs_gpu_status s = launch_hash_files(ix, b, n, c.z, st, [&](size_t f) { return first[f + 1] != first[f]; }); s != COBS_GPU_OK)
+        return s;
+    HIP_TRY(w->ev.mark(1, st));
     for (size_t f = 0; f < nf; ++f) {
         if (first[f + 1] == first[f]) continue;
-        const Part& p = ix->parts[f];
-        HashArgs ha;
-        ha.text = b->d_text;
-        ha.span_off = b->d_span_off;
-        ha.q_len = b->d_qlen;
-        ha.blk_off = b->work[f].blk_off;
-        ha.pages = p.d_tpages;
-        ha.table = b->work[f].table.p;
-        ha.err_query = b->flags.p;
-        ha.nq = (uint32_t)n;
-        ha.npages = p.num_tpages();
-        ha.term_size = p.meta.term_size;
-        ha.canonicalize = p.meta.canonicalize;
-        ha.num_hashes = (uint32_t)p.meta.num_hashes;
-        ha.idx64 = p.idx64 ? 1u : 0u;
-        ha.invalid_bases = ix->invalid_bases;     // (miss / skip: a position whose window holds an invalid character reads 0)
-        ha.findere = c.z;
-        ha.valid = nullptr;
-        HIP_TRY(launch_hash(ha, round_up(b->span_off[n], 1024), st));
-    }
-    HIP_TRY(hipEventRecord(w->ev[1], st));
-    for (size_t f = 0; f < nf; ++f) {
-        if (first[f + 1] == first[f]) continue;
-        const Part& p = ix->parts[f];
         PresenceArgs pa;
+        pa.t = table_ref_for(b, f, ix->parts[f], c.z);
         pa.pairs = w->pairs.p + first[f];
-        pa.table = b->work[f].table.p;
-        pa.blk_off = b->work[f].blk_off;
-        pa.q_len = b->d_qlen;
         pa.bits = w->bits.p;
         pa.npairs = (uint32_t)(first[f + 1] - first[f]);
-        pa.table_npages = p.num_tpages();
-        pa.num_hashes = (uint32_t)p.meta.num_hashes;
-        pa.term_size = p.meta.term_size;
-        pa.findere = c.z;
-        pa.idx64 = p.idx64 ? 1u : 0u;
         HIP_TRY(launch_presence(pa, max_words[f], st));
     }
-    HIP_TRY(hipEventRecord(w->ev[2], st));
+    HIP_TRY(w->ev.mark(2, st));
     HIP_TRY(hipMemcpyAsync(w->h_flags.p, b->flags.p, 16, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(c.bits + word0, w->bits.p, nwords * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    float hm = 0, pm = 0;
-    if (hipEventElapsedTime(&hm, w->ev[0], w->ev[1]) == hipSuccess && hipEventElapsedTime(&pm, w->ev[1], w->ev[2]) == hipSuccess) {
-        w->hash_ms += hm;
-        w->presence_ms += pm;
-        w->passes++;
-    } else {
-        (void)hipGetLastError();
-    }
-    if (w->h_flags.p[0] != 0u) {          // K1 keeps 2^32-1 - (first query with a non-ACGT character)
-        const size_t bad = qsel[std::min<size_t>(0xFFFFFFFFu - w->h_flags.p[0], n - 1)];
-        if (c.bad_query) *c.bad_query = bad;
-        return fail(COBS_GPU_ERR_INVALID_BASE, "Invalid DNA base pair in query string. Only ACGT are allowed. (query " +
-                                               std::to_string(bad) + ")");
-    }
-    return COBS_GPU_OK;
+    if (w->ev.add_elapsed(w->ms)) w->passes++;
+    return invalid_base_from_flags(w->h_flags.p[0], n, c.bad_query, 0, qsel.data());
 }
 
 cobs_gpu_status hit_positions_impl(cobs_gpu_index* ix, const char* const* queries, const size_t* lens, size_t nq,
@@ -187,23 +139,12 @@ cobs_gpu_status hit_positions_impl(cobs_gpu_index* ix, const char* const* querie
         if (hit_offsets[q + 1] < hit_offsets[q]) return fail(COBS_GPU_ERR_ARG, "hit_offsets are not ascending");
     const size_t n_hits = hit_offsets[nq];
     if ((n_hits && !hits) || (cap_words && !bits)) return fail(COBS_GPU_ERR_ARG, "NULL argument");
-    bool streamed = ix->hbm_budget != 0;
-    for (const Part& p : ix->parts) streamed = streamed || p.streamed;
-    if (streamed) return fail(COBS_GPU_ERR_UNSUPPORTED, "positions: not on a handle with an HBM budget (its rows are not all resident)");
+    if (ix->hbm_budget != 0 || any_streamed(ix)) return fail(COBS_GPU_ERR_UNSUPPORTED, "positions: not on a handle with an HBM budget (its rows are not all resident)");
     if (ix->shard_count > 1) return fail(COBS_GPU_ERR_UNSUPPORTED, "positions: not on one shard of several (its rows are not all resident)");
     const uint32_t z = ix->findere;
-    uint32_t max_term = 0;
-    for (const Part& p : ix->parts) max_term = std::max(max_term, p.meta.term_size);
-    // everything the host can refuse is refused before anything is launched
+    // everything the host can refuse is refused before anything is launched (queries without hits are not looked at)
     size_t words = 0;
-    for (size_t q = 0; q < nq; ++q) {
-        if (hit_offsets[q + 1] == hit_offsets[q]) continue;
-        if (bad_query) *bad_query = q;
-        if (!queries[q]) return fail(COBS_GPU_ERR_ARG, "NULL query (query " + std::to_string(q) + ")");
-        if (lens[q] < (size_t)max_term + z)
-            return fail(COBS_GPU_ERR_QUERY_TOO_SHORT, "query too short, needs to be at least " + std::to_string(max_term + z) +
-                        " characters long" + (z ? " with findere z = " + std::to_string(z) : std::string()) +
-                        " (query " + std::to_string(q) + ")");
+    cobs_gpu_status refused = check_query_lengths(ix, queries, lens, nq, z, [&](size_t q) -> cobs_gpu_status {
         if (lens[q] >= 0xFFFFFFF0ull) return fail(COBS_GPU_ERR_QUERY_TOO_LONG, "query too long (query " + std::to_string(q) + ")");
         for (size_t h = hit_offsets[q]; h < hit_offsets[q + 1]; ++h) {
             if (hits[h].file_no >= ix->parts.size())
@@ -215,8 +156,9 @@ cobs_gpu_status hit_positions_impl(cobs_gpu_index* ix, const char* const* querie
             words += (size_t)((npos + 63) / 64);
             bit_offsets[h + 1] = words;
         }
-    }
-    if (bad_query) *bad_query = 0;
+        return COBS_GPU_OK;
+    }, bad_query, [&](size_t q) { return hit_offsets[q + 1] == hit_offsets[q]; });
+    if (refused != COBS_GPU_OK) return refused;
     if (words_needed) *words_needed = words;
     if (words > cap_words) return fail(COBS_GPU_ERR_CAPACITY, "bit buffer too small; *words_needed holds the needed size");
     if (n_hits == 0) return COBS_GPU_OK;
@@ -225,8 +167,7 @@ cobs_gpu_status hit_positions_impl(cobs_gpu_index* ix, const char* const* querie
     // passes: K1's tables (all files of the handle share the pass's queries) and the pairs + words of the pass stay
     // below the search call's workspace limit each
     const uint64_t kLimit = ix->tune.pass_bytes;
-    uint64_t terms_per_char = 0;
-    for (const Part& p : ix->parts) terms_per_char += 4ull * p.meta.num_hashes * std::max<uint32_t>(p.num_tpages(), 1) * (p.idx64 ? 2 : 1);
+    const uint64_t terms_per_char = table_bytes_per_char(ix);
     std::vector<size_t> qsel;
     uint64_t table_bytes = 0, out_bytes = 0;
     for (size_t q = 0; q < nq; ++q) {
@@ -265,10 +206,10 @@ cobs_gpu_status cobs_gpu_positions_ms(cobs_gpu_index* ix, double out[3]) {
     if (!ix || !out) return fail(COBS_GPU_ERR_ARG, "NULL argument");
     out[0] = out[1] = out[2] = 0;
     if (PositionsWork* w = ix->positions) {
-        out[0] = w->presence_ms;
-        out[1] = w->hash_ms;
+        out[0] = w->ms[1];
+        out[1] = w->ms[0];
         out[2] = (double)w->passes;
-        w->presence_ms = w->hash_ms = 0;
+        w->ms[0] = w->ms[1] = 0;
         w->passes = 0;
     }
     return COBS_GPU_OK;

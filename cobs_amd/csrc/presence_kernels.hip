@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 
 #include "presence_kernels.hpp"
+#include "wave_ops.hpp"      // dispatch_idx_flag
 
 namespace cobs_amd {
 
@@ -22,24 +23,21 @@ __global__ __launch_bounds__(256) void presence_kernel(PresenceArgs a) {
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const PresencePair pr = a.pairs[blockIdx.x];          // grid.x == npairs
     const uint32_t q = pr.query;
-    const uint64_t b0 = a.blk_off[q];
-    const uint32_t tblk = (uint32_t)(a.blk_off[q + 1] - b0) + 1u;      // K1 adds one padding block per (query, sub-index)
-    const uint32_t T = a.q_len[q] - a.term_size + 1u;
-    const uint32_t z = a.findere;
+    const uint32_t T = a.t.q_len[q] - a.t.term_size + 1u;
+    const uint32_t z = a.t.findere;
     const uint32_t nwords = (T - z + 63u) >> 6;            // the host made sure T > z
-    const uint32_t H = H1 ? 1u : a.num_hashes;
-    const IdxT* tab = reinterpret_cast<const IdxT*>(a.table) +
-                      ((b0 + q) * a.table_npages + (uint64_t)pr.tpage * tblk) * (8ull * H);
+    const uint32_t H = H1 ? 1u : a.t.num_hashes;
+    const RowTable<IdxT> tab(a.t, q, pr.tpage, H);
 
     auto present = [&](uint32_t t) -> bool {
         if (t >= T) return false;
-        const IdxT* e = tab + (uint64_t)(t >> 3) * (8u * H) + (t & 7u);
+        const IdxT* e = tab.term(t);
         uint32_t acc = 0xFFu;
         if (H1) {
             acc = pr.col[(uint64_t)e[0] * pr.pitch];
         } else {
 #pragma unroll 4
-            for (uint32_t j = 0; j < H; ++j) acc &= pr.col[(uint64_t)e[j * 8u] * pr.pitch];
+            for (uint32_t j = 0; j < H; ++j) acc &= pr.col[(uint64_t)e[j * kRowTableLanes] * pr.pitch];
         }
         return ((acc >> pr.bit) & 1u) != 0u;
     };
@@ -61,14 +59,9 @@ hipError_t launch_presence(const PresenceArgs& a, uint32_t max_words, hipStream_
     // four words per work-group and trip; long queries spread over grid.y, at most four trips per wave up to 4096 words
     const uint32_t gy = max_words <= 16u ? 1u : (max_words + 15u) / 16u > 256u ? 256u : (max_words + 15u) / 16u;
     const dim3 grid(a.npairs, gy), block(256);
-    const bool h1 = a.num_hashes == 1;
-    if (a.idx64) {
-        if (h1) hipLaunchKernelGGL((presence_kernel<uint64_t, true>), grid, block, 0, stream, a);
-        else hipLaunchKernelGGL((presence_kernel<uint64_t, false>), grid, block, 0, stream, a);
-    } else {
-        if (h1) hipLaunchKernelGGL((presence_kernel<uint32_t, true>), grid, block, 0, stream, a);
-        else hipLaunchKernelGGL((presence_kernel<uint32_t, false>), grid, block, 0, stream, a);
-    }
+    dispatch_idx_flag(a.t.idx64 != 0, a.t.num_hashes == 1, [&](auto idx, auto h1) {
+        hipLaunchKernelGGL((presence_kernel<decltype(idx), decltype(h1)::value>), grid, block, 0, stream, a);
+    });
     return hipGetLastError();
 }
 

@@ -5,6 +5,8 @@
 
 #include <cstdint>
 
+#include "row_table.hpp"
+
 namespace cobs_amd {
 
 // One (query, document) pair as the host resolved it: the document's column in the resident chunk that holds it.
@@ -19,17 +21,11 @@ struct PresencePair {
 
 // Arguments of the presence kernel for one index file: the pairs whose document lives in that file.
 struct PresenceArgs {
+    TableRef t;                 // K1's row indices of the file (row_table.hpp); findere z: position p is set when terms
+                                // p .. p + z are all present
     const PresencePair* pairs;
-    const void* table;          // K1's row indices [query][sub-index][block (nblk + 1)][hash][8] (u32, or u64 when idx64)
-    const uint64_t* blk_off;    // nq + 1 prefix sums of 8-term blocks per query (this file's term size)
-    const uint32_t* q_len;      // characters per query
     uint64_t* bits;             // output words: pair i writes ceil((T - z) / 64) words from pairs[i].out
     uint32_t npairs;
-    uint32_t table_npages;      // sub-indexes in the row-index table
-    uint32_t num_hashes;
-    uint32_t term_size;
-    uint32_t findere;           // z (0..7): position p is set when terms p .. p + z are all present
-    uint32_t idx64;
 };
 
 // One work-group of four waves per pair (grid.x), a wave per 64 consecutive terms; max_words = the longest pair's output.

@@ -22,38 +22,9 @@
 #include <algorithm>
 
 #include "prevalence_kernels.hpp"
+#include "wave_ops.hpp"      // group_sum_last, low_bits, dispatch_idx_flag
 
 namespace cobs_amd {
-
-namespace {
-
-template <int CTRL, int ROW_MASK = 0xF, int BANK_MASK = 0xF, bool BOUND_ZERO = true>
-__device__ __forceinline__ uint32_t dpp_mov(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, BANK_MASK, BOUND_ZERO);
-}
-constexpr int kDppQuadXor1 = 0xB1;       // quad_perm:[1,0,3,2]
-constexpr int kDppQuadXor2 = 0x4E;       // quad_perm:[2,3,0,1]
-constexpr int kDppRowMirror = 0x140;     // lane i <- lane 15 - i of its row
-constexpr int kDppHalfMirror = 0x141;    // lane i <- lane 7 - i of its half row
-constexpr int kDppBcast15 = 0x142;       // lane 15 of a row -> every lane of the next row
-constexpr int kDppBcast31 = 0x143;       // lane 31 -> every lane of rows 2 and 3
-
-// sum of `c` over the W (power of two, 1..64) consecutive lanes of a lane group; the LAST lane of the group holds it
-// (up to 16 lanes every lane does).  Every lane of the wave takes part.
-__device__ __forceinline__ uint32_t group_sum_last(uint32_t c, uint32_t W) {
-    if (W >= 2u) c += dpp_mov<kDppQuadXor1>(c);
-    if (W >= 4u) c += dpp_mov<kDppQuadXor2>(c);
-    if (W >= 8u) c += dpp_mov<kDppHalfMirror>(c);
-    if (W >= 16u) c += dpp_mov<kDppRowMirror>(c);
-    if (W >= 32u) c += dpp_mov<kDppBcast15, 0xA, 0xF, false>(c);      // rows 1 and 3 += the total of the row before
-    if (W >= 64u) c += dpp_mov<kDppBcast31, 0xC, 0xF, false>(c);      // rows 2 and 3 += the total of the first half
-    return c;
-}
-
-// the low r bits (r >= 32: all)
-__device__ __forceinline__ uint32_t low_bits(uint32_t r) { return r >= 32u ? 0xFFFFFFFFu : (1u << r) - 1u; }
-
-}  // namespace
 
 // H1: one hash function (the COBS default), no loop over the hashes
 template <typename IdxT, bool H1>
@@ -67,13 +38,10 @@ __global__ __launch_bounds__(256) void prevalence_kernel(PrevalenceArgs a) {
     // 8 * valid_bytes live documents; test_gpu_prevalence.py's unmasked fixture found it)
     if (a.num_docs <= pd.doc0 || pd.valid_bytes == 0u) return;      // (uniform: a slice of padding documents only)
     const uint32_t live = min(a.num_docs - pd.doc0, pd.valid_bytes * 8u);
-    const uint64_t b0 = a.blk_off[q];
-    const uint32_t tblk = (uint32_t)(a.blk_off[q + 1] - b0) + 1u;      // K1 adds one padding block per (query, sub-index)
-    const uint32_t z = a.findere;
-    const uint32_t n = a.q_len[q] - a.term_size + 1u - z;   // the host made sure T > z
-    const uint32_t H = H1 ? 1u : a.num_hashes;
-    const IdxT* __restrict__ tab = reinterpret_cast<const IdxT*>(a.table) +
-                                   ((b0 + q) * a.table_npages + (uint64_t)pd.tpage * tblk) * (8ull * H);
+    const uint32_t z = a.t.findere;
+    const uint32_t n = a.t.q_len[q] - a.t.term_size + 1u - z;   // the host made sure T > z
+    const uint32_t H = H1 ? 1u : a.t.num_hashes;
+    const RowTable<IdxT> tab(a.t, q, pd.tpage, H);
     const uint8_t* __restrict__ rows = a.data + pd.base;
     uint32_t* __restrict__ out = a.out + a.seg_off[(uint64_t)q * a.seg_stride];
     const uint32_t lx = a.lx, ly = a.ly;
@@ -86,14 +54,13 @@ __global__ __launch_bounds__(256) void prevalence_kernel(PrevalenceArgs a) {
         uint4 acc = make_uint4(~0u, ~0u, ~0u, ~0u);
         const uint8_t* col = rows + (uint64_t)chunk * 16u;
         for (uint32_t s = 0; s <= z; ++s) {
-            const uint32_t t = p + s;
-            const IdxT* e = tab + (uint64_t)(t >> 3) * (8u * H) + (t & 7u);
+            const IdxT* e = tab.term(p + s);
             if (H1) {
                 const uint4 x = *reinterpret_cast<const uint4*>(col + (uint64_t)e[0] * a.pitch);
                 acc.x &= x.x; acc.y &= x.y; acc.z &= x.z; acc.w &= x.w;
             } else {
                 for (uint32_t j = 0; j < H; ++j) {
-                    const uint4 x = *reinterpret_cast<const uint4*>(col + (uint64_t)e[j * 8u] * a.pitch);
+                    const uint4 x = *reinterpret_cast<const uint4*>(col + (uint64_t)e[j * kRowTableLanes] * a.pitch);
                     acc.x &= x.x; acc.y &= x.y; acc.z &= x.z; acc.w &= x.w;
                 }
             }
@@ -156,17 +123,12 @@ hipError_t launch_prevalence(PrevalenceArgs a, const std::vector<PageDev>& pages
     const uint32_t groups = (max_positions + a.ly - 1u) / a.ly;
     const uint32_t gy = std::min(1024u, (groups + 31u) / 32u);
     constexpr size_t kMaxGridZ = 65535;
-    const bool h1 = a.num_hashes == 1;
     for (size_t p0 = 0; p0 < pages.size(); p0 += kMaxGridZ) {
         a.page0 = (uint32_t)p0;
         const dim3 grid(nq, gy, (uint32_t)std::min(kMaxGridZ, pages.size() - p0)), block(256);
-        if (a.idx64) {
-            if (h1) hipLaunchKernelGGL((prevalence_kernel<uint64_t, true>), grid, block, 0, stream, a);
-            else hipLaunchKernelGGL((prevalence_kernel<uint64_t, false>), grid, block, 0, stream, a);
-        } else {
-            if (h1) hipLaunchKernelGGL((prevalence_kernel<uint32_t, true>), grid, block, 0, stream, a);
-            else hipLaunchKernelGGL((prevalence_kernel<uint32_t, false>), grid, block, 0, stream, a);
-        }
+        dispatch_idx_flag(a.t.idx64 != 0, a.t.num_hashes == 1, [&](auto idx, auto h1) {
+            hipLaunchKernelGGL((prevalence_kernel<decltype(idx), decltype(h1)::value>), grid, block, 0, stream, a);
+        });
         if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     }
     return hipSuccess;

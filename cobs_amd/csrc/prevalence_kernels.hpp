@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "device_types.hpp"
+#include "row_table.hpp"
 
 namespace cobs_amd {
 
@@ -14,22 +15,16 @@ namespace cobs_amd {
 struct PrevalenceArgs {
     const uint8_t* data;        // the chunk's buffer
     const PageDev* pages;       // its pages: base, doc0, valid_bytes, tpage (row `sig` is the zero row K1 names for absent terms)
-    const void* table;          // K1's row indices [query][sub-index][block (nblk + 1)][hash][8] (u32, or u64 when idx64)
-    const uint64_t* blk_off;    // nq + 1 prefix sums of 8-term blocks per query (this file's term size)
-    const uint32_t* q_len;      // characters per query
+    TableRef t;                 // K1's row indices of the file (row_table.hpp); findere z: position p is set when terms
+                                // p .. p + z are all present
     const uint64_t* seg_off;    // first cell of query q in this file: seg_off[q * seg_stride]
     uint32_t* out;              // cells of the pass: out[seg_off[q * seg_stride] + p] += documents of the slice that hold position p
     uint32_t seg_stride;        // files of the handle
     uint32_t page0;             // blockIdx.z + page0 = the page
     uint32_t pitch;             // bytes between rows (a multiple of 16)
-    uint32_t table_npages;      // sub-indexes in the row-index table
-    uint32_t num_hashes;
-    uint32_t term_size;
-    uint32_t findere;           // z (0..7): position p is set when terms p .. p + z are all present
     uint32_t num_docs;          // real documents of the file: slots at or beyond it never count
     uint32_t lx;                // lanes side by side along a row (16-byte chunks): a power of two, 1..64
     uint32_t ly;                // positions a wave takes side by side: 64 / lx
-    uint32_t idx64;
 };
 
 // lanes of a wave along a row of `valid_bytes` bytes: the next power of two of its 16-byte chunks, at most 64 (wider

@@ -78,12 +78,7 @@ cobs_gpu_status meta_wait(cobs_gpu_batch* b, cobs_gpu_comm* c, Agreed* a) {
 }
 
 cobs_gpu_status make_scratch(cobs_gpu_index* ix, int slot) {
-    if (ix->scratch[slot]) return COBS_GPU_OK;
-    cobs_gpu_status cs = cobs_gpu_batch_create(ix, 0, 0, &ix->scratch[slot]);
-    if (cs != COBS_GPU_OK) return cs;
-    HIP_TRY(hipStreamCreateWithFlags(&ix->scratch[slot]->own_stream, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreateWithFlags(&ix->scratch[slot]->done, hipEventDisableTiming));
-    return COBS_GPU_OK;
+    return scratch_batch(ix, slot);
 }
 
 // ClassicSearch::search over the sharded index: every rank calls this with the same queries and
@@ -262,12 +257,7 @@ cobs_gpu_status sharded_search_impl(cobs_gpu_index* ix, cobs_gpu_comm* c, const 
                 if (carried) return fail((cobs_gpu_status)carried, carried_msg);
                 return fail(COBS_GPU_ERR_RCCL, "the pass failed on another rank (status " + std::to_string(ag.worst) + ")");
             }
-            if (ag.bad_word != 0u) {
-                const size_t bad = ps.g0 + (size_t)(0xFFFFFFFFu - ag.bad_word);
-                if (bad_query) *bad_query = bad;
-                return fail(COBS_GPU_ERR_INVALID_BASE, "Invalid DNA base pair in query string. Only ACGT are allowed. (query " +
-                                                       std::to_string(bad) + ")");
-            }
+            if (cobs_gpu_status is = invalid_base_from_flags(ag.bad_word, ps.g1 - ps.g0, bad_query, ps.g0); is != COBS_GPU_OK) return is;
             b->synced = true;                    // (the flag words are home: what cobs_gpu_batch_sync would have fetched)
             Exchange& x = *b->xchg;
             if (b->topk_k) {
@@ -586,9 +576,7 @@ cobs_gpu_status cobs_gpu_sharded_batch_sync(cobs_gpu_sharded_batch* sb, size_t* 
             const cobs_gpu_status s = cobs_gpu_batch_sync(b, sb->scan, &bad);
             if (s != COBS_GPU_OK && first == COBS_GPU_OK) {
                 first = s;
-                keep = s == COBS_GPU_ERR_INVALID_BASE ? "Invalid DNA base pair in query string. Only ACGT are allowed. (query " +
-                                                        std::to_string(sb->q0[i] + bad) + ")"
-                                                      : last_error_text();
+                keep = s == COBS_GPU_ERR_INVALID_BASE ? invalid_base_message(sb->q0[i] + bad) : last_error_text();
                 if (bad_query) *bad_query = sb->q0[i] + bad;
             }
         }

@@ -27,12 +27,9 @@ struct WeightedWork {
     DevBuf<unsigned long long> fill;
     PinnedBuf<uint64_t> h_seg_off, h_total;
     PinnedBuf<uint32_t> h_flags;            // K1's flag words | the pool's 64-bit fill
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // before K1 | prevalence | weights | scan | after it
+    PhaseEvents<5> ev;                      // before K1 | prevalence | weights | scan | after it
     double ms[4] = {0, 0, 0, 0};            // hash | prevalence | weights | scan
     uint64_t passes = 0;
-    ~WeightedWork() {
-        for (auto& e : ev) if (e) (void)hipEventDestroy(e);
-    }
 };
 
 void destroy_weighted_work(WeightedWork* w) { delete w; }
@@ -59,9 +56,7 @@ cobs_gpu_status launch_scans(const Call& c, WeightedWork* w, cobs_gpu_batch* b, 
     for (size_t f = 0; f < nf; ++f) {
         const Part& p = ix->parts[f];
         WeightedScanArgs sa{};
-        sa.table = b->work[f].table.p;
-        sa.blk_off = b->work[f].blk_off;
-        sa.q_len = b->d_qlen;
+        sa.t = table_ref_for(b, f, p, c.z);
         sa.seg_off = w->seg_off.p + f;
         sa.weights = w->weights.p;
         sa.thr = w->thr.p + f * n;
@@ -70,16 +65,10 @@ cobs_gpu_status launch_scans(const Call& c, WeightedWork* w, cobs_gpu_batch* b, 
         sa.cap = pool_cap;
         sa.seg_stride = (uint32_t)nf;
         sa.nq = (uint32_t)n;
-        sa.table_npages = p.num_tpages();
-        sa.num_hashes = (uint32_t)p.meta.num_hashes;
-        sa.term_size = p.meta.term_size;
-        sa.findere = c.z;
         sa.num_docs = (uint32_t)p.meta.doc_names.size();
         sa.file_no = (uint32_t)f;
-        sa.idx64 = p.idx64 ? 1u : 0u;
         const int planes = weighted_planes_for(max_len - p.meta.term_size + 1 - c.z);
-        for (const Chunk& ch : p.chunks) {
-            if (!ch.d_data || ch.pages.empty()) continue;
+        cobs_gpu_status s = for_each_resident_chunk(p, [&](const Chunk& ch) -> cobs_gpu_status {
             sa.data = ch.d_data;
             sa.pages = ch.d_pages;
             sa.pitch = ch.pitch;
@@ -87,7 +76,9 @@ cobs_gpu_status launch_scans(const Call& c, WeightedWork* w, cobs_gpu_batch* b, 
             sa.total_chunks = ch.total_chunks;
             sa.tile_w = weighted_tile_w(ch.total_chunks);
             HIP_TRY(launch_weighted_scan(sa, planes, st));
-        }
+            return COBS_GPU_OK;
+        });
+        if (s != COBS_GPU_OK) return s;
     }
     return COBS_GPU_OK;
 }
@@ -98,14 +89,9 @@ cobs_gpu_status run_pass(const Call& c, size_t q0, size_t q1) {
     HIP_TRY(hipSetDevice(ix->device));
     if (!ix->weighted) ix->weighted = new WeightedWork;
     WeightedWork* w = ix->weighted;
-    for (auto& e : w->ev) if (!e) HIP_TRY(hipEventCreate(&e));
-    if (!ix->scratch[0]) {          // the workspace of the host-buffer calls (host_api.cpp): query upload and K1's tables
-        cobs_gpu_status st = cobs_gpu_batch_create(ix, 0, 0, &ix->scratch[0]);
-        if (st != COBS_GPU_OK) return st;
-        HIP_TRY(hipStreamCreateWithFlags(&ix->scratch[0]->own_stream, hipStreamNonBlocking));
-        HIP_TRY(hipEventCreateWithFlags(&ix->scratch[0]->done, hipEventDisableTiming));
-    }
-    cobs_gpu_batch* b = ix->scratch[0];
+    HIP_TRY(w->ev.create());
+    cobs_gpu_batch* b = nullptr;
+    if (cobs_gpu_status s = scratch_batch(ix, 0, &b); s != COBS_GPU_OK) return s;
     hipStream_t st = b->own_stream;
     const size_t n = q1 - q0, nf = ix->parts.size();
     size_t bad_local = 0;
@@ -151,57 +137,12 @@ cobs_gpu_status run_pass(const Call& c, size_t q0, size_t q1) {
 
     HIP_TRY(hipMemcpyAsync(w->seg_off.p, w->h_seg_off.p, (n * nf + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
     HIP_TRY(launch_clear_flags(b->flags.p, st));
-    HIP_TRY(launch_prevalence_zero(w->cells.p, ncells, st));
     HIP_TRY(launch_prevalence_zero(reinterpret_cast<uint32_t*>(w->fill.p), 2, st));
-    HIP_TRY(hipEventRecord(w->ev[0], st));
-    for (size_t f = 0; f < nf; ++f) {
-        const Part& p = ix->parts[f];
-        if (p.num_tpages() == 0) continue;
-        HashArgs ha;
-        ha.text = b->d_text;
-        ha.span_off = b->d_span_off;
-        ha.q_len = b->d_qlen;
-        ha.blk_off = b->work[f].blk_off;
-        ha.pages = p.d_tpages;
-        ha.table = b->work[f].table.p;
-        ha.err_query = b->flags.p;
-        ha.nq = (uint32_t)n;
-        ha.npages = p.num_tpages();
-        ha.term_size = p.meta.term_size;
-        ha.canonicalize = p.meta.canonicalize;
-        ha.num_hashes = (uint32_t)p.meta.num_hashes;
-        ha.idx64 = p.idx64 ? 1u : 0u;
-        ha.invalid_bases = ix->invalid_bases;     // (miss / skip: a position whose window holds an invalid character reads 0)
-        ha.findere = c.z;
-        ha.valid = nullptr;
-        HIP_TRY(launch_hash(ha, round_up(b->span_off[n], 1024), st));
-    }
-    HIP_TRY(hipEventRecord(w->ev[1], st));
-    for (size_t f = 0; f < nf; ++f) {
-        const Part& p = ix->parts[f];
-        PrevalenceArgs pa{};
-        pa.table = b->work[f].table.p;
-        pa.blk_off = b->work[f].blk_off;
-        pa.q_len = b->d_qlen;
-        pa.seg_off = w->seg_off.p + f;
-        pa.out = w->cells.p;
-        pa.seg_stride = (uint32_t)nf;
-        pa.table_npages = p.num_tpages();
-        pa.num_hashes = (uint32_t)p.meta.num_hashes;
-        pa.term_size = p.meta.term_size;
-        pa.findere = c.z;
-        pa.num_docs = (uint32_t)p.meta.doc_names.size();
-        pa.idx64 = p.idx64 ? 1u : 0u;
-        const uint32_t max_positions = (uint32_t)(max_len - p.meta.term_size + 1 - c.z);
-        for (const Chunk& ch : p.chunks) {
-            if (!ch.d_data || ch.pages.empty()) continue;
-            pa.data = ch.d_data;
-            pa.pages = ch.d_pages;
-            pa.pitch = ch.pitch;
-            HIP_TRY(launch_prevalence(pa, ch.pages, (uint32_t)n, max_positions, st));
-        }
-    }
-    HIP_TRY(hipEventRecord(w->ev[2], st));
+    // K1 and the prevalence of every position into the cells, exactly as cobs_gpu_prevalence fills its own
+    if (cobs_gpu_status s = launch_prevalence_cells(ix, b, w->seg_off.p, w->cells.p, ncells, n, max_len, c.z, st, w->ev.ev[0], w->ev.ev[1]);
+        s != COBS_GPU_OK)
+        return s;
+    HIP_TRY(w->ev.mark(2, st));
     for (size_t f = 0; f < nf; ++f) {
         const Part& p = ix->parts[f];
         WeightArgs wa{};
@@ -218,41 +159,27 @@ cobs_gpu_status run_pass(const Call& c, size_t q0, size_t q1) {
         wa.num_docs = (uint32_t)p.meta.doc_names.size();
         HIP_TRY(launch_weights(wa, (uint32_t)n, st));
     }
-    HIP_TRY(hipEventRecord(w->ev[3], st));
+    HIP_TRY(w->ev.mark(3, st));
     if (cobs_gpu_status s = launch_scans(c, w, b, n, max_len, pool_cap, st); s != COBS_GPU_OK) return s;
-    HIP_TRY(hipEventRecord(w->ev[4], st));
+    HIP_TRY(w->ev.mark(4, st));
     HIP_TRY(hipMemcpyAsync(w->h_flags.p, b->flags.p, 16, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(w->h_flags.p + 4, w->fill.p, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(w->h_total.p, w->total.p, n * nf * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    float t[4] = {0, 0, 0, 0};
-    bool timed = true;
-    for (int i = 0; i < 4; ++i) timed = timed && hipEventElapsedTime(&t[i], w->ev[i], w->ev[i + 1]) == hipSuccess;
-    if (timed) {
-        for (int i = 0; i < 4; ++i) w->ms[i] += t[i];
-        w->passes++;
-    } else {
-        (void)hipGetLastError();
-    }
-    if (w->h_flags.p[0] != 0u) {          // K1 keeps 2^32-1 - (first query with a non-ACGT character)
-        const size_t bad = q0 + std::min<size_t>(0xFFFFFFFFu - w->h_flags.p[0], n - 1);
-        if (c.bad_query) *c.bad_query = bad;
-        return fail(COBS_GPU_ERR_INVALID_BASE, "Invalid DNA base pair in query string. Only ACGT are allowed. (query " +
-                                               std::to_string(bad) + ")");
-    }
+    if (w->ev.add_elapsed(w->ms)) w->passes++;
+    if (cobs_gpu_status s = invalid_base_from_flags(w->h_flags.p[0], n, c.bad_query, q0); s != COBS_GPU_OK) return s;
     uint64_t fill = (uint64_t)w->h_flags.p[5] << 32 | w->h_flags.p[4];
     if (fill > pool_cap) {
         // overflow: the pool grows to the reported fill and the scan of this pass alone runs again (cells and weights stay)
         pool_cap = fill;
         if (cobs_gpu_status s = reserve_pool(); s != COBS_GPU_OK) return s;
         HIP_TRY(launch_prevalence_zero(reinterpret_cast<uint32_t*>(w->fill.p), 2, st));
-        HIP_TRY(hipEventRecord(w->ev[3], st));
+        HIP_TRY(w->ev.mark(3, st));
         if (cobs_gpu_status s = launch_scans(c, w, b, n, max_len, pool_cap, st); s != COBS_GPU_OK) return s;
-        HIP_TRY(hipEventRecord(w->ev[4], st));
+        HIP_TRY(w->ev.mark(4, st));
         HIP_TRY(hipMemcpyAsync(w->h_flags.p + 4, w->fill.p, 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
-        if (hipEventElapsedTime(&t[3], w->ev[3], w->ev[4]) == hipSuccess) w->ms[3] += t[3];
-        else (void)hipGetLastError();
+        (void)w->ev.add_elapsed(w->ms, 3, 4);
         fill = (uint64_t)w->h_flags.p[5] << 32 | w->h_flags.p[4];
         if (fill > pool_cap) return fail(COBS_GPU_ERR_HIP, "weighted: the hit pool overflowed twice");
     }
@@ -272,32 +199,22 @@ cobs_gpu_status search_weighted_impl(cobs_gpu_index* ix, const char* const* quer
     if (!ix || !hit_offsets) return fail(COBS_GPU_ERR_ARG, "NULL argument");
     if ((nq && (!queries || !lens)) || (cap && !hits)) return fail(COBS_GPU_ERR_ARG, "NULL argument");
     if (nq >= 0xFFFFFFF0ull) return fail(COBS_GPU_ERR_ARG, "too many queries");
-    bool streamed = ix->hbm_budget != 0;
-    for (const Part& p : ix->parts) streamed = streamed || p.streamed;
-    if (streamed) return fail(COBS_GPU_ERR_UNSUPPORTED, "weighted: not on a handle with an HBM budget (its rows are not all resident)");
+    if (ix->hbm_budget != 0 || any_streamed(ix)) return fail(COBS_GPU_ERR_UNSUPPORTED, "weighted: not on a handle with an HBM budget (its rows are not all resident)");
     if (ix->shard_count > 1) return fail(COBS_GPU_ERR_UNSUPPORTED, "weighted: not on one shard of several (the weights need every shard's counts)");
     for (size_t q = 0; q <= nq; ++q) hit_offsets[q] = 0;
     const size_t nf = ix->parts.size();
     const uint32_t z = ix->findere;
-    uint32_t max_term = 0, min_term = 0xFFFFFFFFu;
-    for (const Part& p : ix->parts) {
-        max_term = std::max(max_term, p.meta.term_size);
-        min_term = std::min(min_term, p.meta.term_size);
-    }
+    uint32_t min_term = 0xFFFFFFFFu;
+    for (const Part& p : ix->parts) min_term = std::min(min_term, p.meta.term_size);
     // everything the host can refuse is refused before anything is launched
-    for (size_t q = 0; q < nq; ++q) {
-        if (bad_query) *bad_query = q;
-        if (!queries[q]) return fail(COBS_GPU_ERR_ARG, "NULL query (query " + std::to_string(q) + ")");
-        if (lens[q] < (size_t)max_term + z)
-            return fail(COBS_GPU_ERR_QUERY_TOO_SHORT, "query too short, needs to be at least " + std::to_string(max_term + z) +
-                        " characters long" + (z ? " with findere z = " + std::to_string(z) : std::string()) +
-                        " (query " + std::to_string(q) + ")");
+    cobs_gpu_status refused = check_query_lengths(ix, queries, lens, nq, z, [&](size_t q) -> cobs_gpu_status {
         // 15 * n stays below 2^20, the counter planes of the scan
         if (nf && lens[q] - min_term + 1 - z > kWeightedMaxPositions)
             return fail(COBS_GPU_ERR_QUERY_TOO_LONG, "query too long: weighted search scores at most " +
                         std::to_string(kWeightedMaxPositions) + " positions (query " + std::to_string(q) + ")");
-    }
-    if (bad_query) *bad_query = 0;
+        return COBS_GPU_OK;
+    }, bad_query);
+    if (refused != COBS_GPU_OK) return refused;
     if (total_weight) std::fill(total_weight, total_weight + nq * nf, 0ull);
     if (nq == 0 || nf == 0) return COBS_GPU_OK;
 
@@ -311,8 +228,7 @@ cobs_gpu_status search_weighted_impl(cobs_gpu_index* ix, const char* const* quer
     // passes: K1's tables, 5 bytes per position and file, and -- when every document comes back -- the pool's records stay
     // below the search call's workspace limit
     const uint64_t kLimit = ix->tune.pass_bytes;
-    uint64_t terms_per_char = 0;
-    for (const Part& p : ix->parts) terms_per_char += 4ull * p.meta.num_hashes * std::max<uint32_t>(p.num_tpages(), 1) * (p.idx64 ? 2 : 1);
+    const uint64_t terms_per_char = table_bytes_per_char(ix);
     const uint64_t pool_bytes = threshold > 0.0 ? 0 : real_total * sizeof(HitDev);
     size_t first = 0;
     uint64_t bytes = 0;

@@ -29,18 +29,11 @@
 #include <algorithm>
 
 #include "weighted_kernels.hpp"
+#include "wave_ops.hpp"      // csa, low_bits, dispatch_idx_flag
 
 namespace cobs_amd {
 
 namespace {
-
-// carry-save adder: (h, l) = a + b + c per bit position; majority (0xE8) and parity (0x96) are one v_bitop3_b32 each
-__device__ __forceinline__ void csa(uint32_t& h, uint32_t& l, uint32_t a, uint32_t b, uint32_t c) {
-    const uint32_t hh = __builtin_amdgcn_bitop3_b32(a, b, c, 0xE8);
-    const uint32_t ll = __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
-    h = hh;
-    l = ll;
-}
 
 // eight words into the three planes p[0..2]; returns the carry into the plane above them
 __device__ __forceinline__ uint32_t absorb8(uint32_t* p, const uint32_t (&x)[8]) {
@@ -115,9 +108,6 @@ __device__ __forceinline__ void issue_rows(uint4 (&X)[8], const uint8_t* lane_ba
     }
 }
 
-// the low r bits (r >= 32: all)
-__device__ __forceinline__ uint32_t low_bits(uint32_t r) { return r >= 32u ? 0xFFFFFFFFu : (1u << r) - 1u; }
-
 }  // namespace
 
 __global__ __launch_bounds__(256) void weight_kernel(WeightArgs a) {
@@ -170,13 +160,10 @@ __global__ __launch_bounds__(256) void weighted_scan_kernel(WeightedScanArgs a) 
     const PageDev pd = a.pages[pg];
     const uint8_t* lane_base = a.data + pd.base + (uint64_t)ch * 16u;
     const uint32_t pitch = a.pitch;
-    const uint64_t b0 = a.blk_off[q];
-    const uint32_t nblk_q = (uint32_t)(a.blk_off[q + 1] - b0);          // K1 adds one padding block behind them
-    const uint32_t H = FAST ? 1u : a.num_hashes, z = FAST ? 0u : a.findere;
-    const IdxT* __restrict__ tab = reinterpret_cast<const IdxT*>(a.table) +
-                                   ((b0 + q) * a.table_npages + (uint64_t)pd.tpage * (nblk_q + 1u)) * (8ull * H);
-    const uint32_t n = a.q_len[q] - a.term_size + 1u - z;
-    const uint32_t nb = (n + 7u) >> 3;                                  // blocks of positions (<= nblk_q)
+    const uint32_t H = FAST ? 1u : a.t.num_hashes, z = FAST ? 0u : a.t.findere;
+    const RowTable<IdxT> tab(a.t, q, pd.tpage, H);
+    const uint32_t n = a.t.q_len[q] - a.t.term_size + 1u - z;
+    const uint32_t nb = (n + 7u) >> 3;                                  // blocks of positions (<= tab.nblk)
     const uint8_t* __restrict__ wts = a.weights + a.seg_off[(uint64_t)q * a.seg_stride];
     const uint32_t vw = wave * G + grp, NV = 4u * G;
 
@@ -193,7 +180,7 @@ __global__ __launch_bounds__(256) void weighted_scan_kernel(WeightedScanArgs a) 
     if constexpr (FAST) {
         auto idx_of = [&](uint32_t i) -> const IdxT* {
             const uint32_t b = vw + i * NV;
-            return tab + (uint64_t)(b < nb ? b : nblk_q) * 8u;
+            return tab.block(b < nb ? b : tab.padding_block());
         };
         auto wts_of = [&](uint32_t i) -> uint2 {
             const uint32_t b = vw + i * NV;
@@ -237,9 +224,9 @@ __global__ __launch_bounds__(256) void weighted_scan_kernel(WeightedScanArgs a) 
                 uint4 acc = make_uint4(~0u, ~0u, ~0u, ~0u);
                 for (uint32_t s = 0; s <= z; ++s) {
                     const uint32_t term = p + s;
-                    const IdxT* e = tab + (uint64_t)(term >> 3) * (8u * H) + (term & 7u);
+                    const IdxT* e = tab.term(term);
                     for (uint32_t j = 0; j < H; ++j) {
-                        const uint4 x = load_row(lane_base, (uint64_t)e[j * 8u], pitch);
+                        const uint4 x = load_row(lane_base, (uint64_t)e[j * kRowTableLanes], pitch);
                         acc.x &= x.x; acc.y &= x.y; acc.z &= x.z; acc.w &= x.w;
                     }
                 }
@@ -363,14 +350,9 @@ namespace {
 
 template <int NP>
 void launch_np(const WeightedScanArgs& a, dim3 grid, hipStream_t stream) {
-    const bool fast = a.num_hashes == 1 && a.findere == 0;
-    if (a.idx64) {
-        if (fast) hipLaunchKernelGGL((weighted_scan_kernel<NP, uint64_t, true>), grid, dim3(256), 0, stream, a);
-        else hipLaunchKernelGGL((weighted_scan_kernel<NP, uint64_t, false>), grid, dim3(256), 0, stream, a);
-    } else {
-        if (fast) hipLaunchKernelGGL((weighted_scan_kernel<NP, uint32_t, true>), grid, dim3(256), 0, stream, a);
-        else hipLaunchKernelGGL((weighted_scan_kernel<NP, uint32_t, false>), grid, dim3(256), 0, stream, a);
-    }
+    dispatch_idx_flag(a.t.idx64 != 0, a.t.num_hashes == 1 && a.t.findere == 0, [&](auto idx, auto fast) {
+        hipLaunchKernelGGL((weighted_scan_kernel<NP, decltype(idx), decltype(fast)::value>), grid, dim3(256), 0, stream, a);
+    });
 }
 
 }  // namespace
@@ -378,7 +360,7 @@ void launch_np(const WeightedScanArgs& a, dim3 grid, hipStream_t stream) {
 hipError_t launch_weighted_scan(WeightedScanArgs a, int planes, hipStream_t stream) {
     if (a.nq == 0 || a.total_chunks == 0) return hipSuccess;
     if (a.pitch == 0 || a.pitch % 16u != 0 || a.cpp != a.pitch / 16u || a.total_chunks % a.cpp != 0 || a.nq > 0x7FFFFFFFu ||
-        a.tile_w == 0 || a.tile_w > 64u || (a.tile_w & (a.tile_w - 1u)) != 0 || a.num_hashes == 0 || a.findere > 7u)
+        a.tile_w == 0 || a.tile_w > 64u || (a.tile_w & (a.tile_w - 1u)) != 0 || a.t.num_hashes == 0 || a.t.findere > 7u)
         return hipErrorInvalidValue;
     const uint32_t ntiles = (a.total_chunks + a.tile_w - 1u) / a.tile_w;
     const uint32_t per_launch = std::max(1u, 0x7FFFFFFFu / a.nq);

@@ -7,6 +7,7 @@
 #include <cstdint>
 
 #include "device_types.hpp"
+#include "row_table.hpp"
 
 namespace cobs_amd {
 
@@ -45,9 +46,7 @@ struct WeightArgs {
 struct WeightedScanArgs {
     const uint8_t* data;        // the chunk's buffer
     const PageDev* pages;       // its pages
-    const void* table;          // K1's row indices [query][sub-index][block (nblk + 1)][hash][8] (u32, or u64 when idx64)
-    const uint64_t* blk_off;    // nq + 1 prefix sums of 8-term blocks per query
-    const uint32_t* q_len;      // characters per query
+    TableRef t;                 // K1's row indices of the file (row_table.hpp)
     const uint64_t* seg_off;    // first weight of query q in this file: seg_off[q * seg_stride] (a multiple of 8; the
                                 // segment is padded to a multiple of 8 with weights of 0)
     const uint8_t* weights;
@@ -62,13 +61,8 @@ struct WeightedScanArgs {
     uint32_t total_chunks;      // pages * cpp
     uint32_t tile_w;            // 16-byte chunks per tile: a power of two, 1..64
     uint32_t tile0;             // blockIdx.x / nq + tile0 = the tile
-    uint32_t table_npages;
-    uint32_t num_hashes;
-    uint32_t term_size;
-    uint32_t findere;
     uint32_t num_docs;          // real documents of the file
     uint32_t file_no;
-    uint32_t idx64;
 };
 
 // counter planes of the scan for a longest query of `max_positions` positions: 8, 12, 14, 16 or 20 (0: too long)

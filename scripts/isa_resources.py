@@ -14,15 +14,18 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+KERNEL_FILES = ("kernels", "group_kernels", "fill_kernels", "prevalence_kernels", "weighted_kernels", "presence_kernels",
+                "fetch_kernels")
 
 
 def main():
     out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "isa_resources.txt")
     # the scan kernels, the grouped-search kernels (group_kernels.hip: accumulate, select, zero) and the filter-fill
-    # kernels (fill_kernels.hip: count, its load-only probe, zero), the prevalence kernels (prevalence_kernels.hip) and the
-    # kernels of the weighted search (weighted_kernels.hip: weights, weighted scan)
+    # kernels (fill_kernels.hip: count, its load-only probe, zero), the prevalence kernels (prevalence_kernels.hip), the
+    # kernels of the weighted search (weighted_kernels.hip: weights, weighted scan), and the other readers of K1's
+    # row-index table (row_table.hpp): the presence kernel and the out-of-core fetch kernels
     asm = ""
-    for name in ("kernels", "group_kernels", "fill_kernels", "prevalence_kernels", "weighted_kernels"):
+    for name in KERNEL_FILES:
         src = os.path.join(ROOT, "cobs_amd", "csrc", name + ".hip")
         with tempfile.TemporaryDirectory() as tmp:
             subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
@@ -49,7 +52,8 @@ def main():
         rows.append((dem, vg, ag, int(g("sgpr_count")), int(g("group_segment_fixed_size")),
                      int(g("private_segment_fixed_size")), g("vgpr_spill_count"), waves))
     rows.sort()
-    lines = ["# kernels.hip, group_kernels.hip, fill_kernels.hip, prevalence_kernels.hip, weighted_kernels.hip @ %s, hipcc -O3 --offload-arch=gfx950; from the code object metadata (.s of --save-temps)" % head,
+    lines = ["# %s @ %s, hipcc -O3 --offload-arch=gfx950; from the code object metadata (.s of --save-temps)"
+             % (", ".join(n + ".hip" for n in KERNEL_FILES), head),
              "# static_lds excludes the dynamic LDS a launch adds (scan_kernel: merge buffers + expansion table)",
              "%-64s %5s %5s %5s %10s %8s %6s %10s" % ("kernel", "vgpr", "agpr", "sgpr", "static_lds", "scratch", "spill",
                                                      "waves/SIMD")]
