@@ -27,7 +27,7 @@ namespace {
 constexpr uint64_t kOffsetMask = (1ull << kAbundanceOffsetBits) - 1ull;
 constexpr uint64_t kKeySeed = 0x5851F42D4C957F2DULL;      // the table's XXH64 seed (the rows use 0 .. H-1)
 
-// the splitmix64 finaliser (kernels.hip's mix64, which stays where it is)
+// the splitmix64 finaliser (build_kernels.hip's mix64, which stays where it is)
 __device__ __forceinline__ uint64_t ab_mix64(uint64_t z) {
     z += 0x9E3779B97F4A7C15ULL;
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;

@@ -90,7 +90,7 @@ struct ScanArgs {
     uint32_t lds_staged;        // measured variant: rows travel HBM -> LDS -> VGPR (global_load_lds)
     uint32_t exp;               // bit field of experimental variants under A/B measurement (tuning key "exp")
     // findere (0..7): a position counts only when z + 1 consecutive terms are present; 0 = the plain count.
-    // z > 0 launches the findere instantiations of K2 (kernels.hip: FZ)
+    // z > 0 launches the findere instantiations of K2 (kernels.hip: FZ; instantiated in scan_findere.hip)
     uint32_t findere;
     // run_topk without score rows: every tile leaves its topk_k best (document, score) candidates at
     // cand[query * cand_stride + (tile_base + tile) * topk_k ..]; nullptr = the other epilogues

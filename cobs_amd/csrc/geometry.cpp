@@ -1,7 +1,7 @@
 // cobs_amd/csrc/geometry.cpp -- the launch geometry of the scan kernel (tile width, waves per work-group, multi-query
 // groups) as a function of the chunk and the batch.  Kept apart from plan.cpp (shards, chunks, budgets) because this
-// function, together with kernels.hip, is what the measured memory traffic of a workload depends on: bench.py stamps
-// its lines with a hash of exactly these two files and replays profiles/traffic.json only for the same hash.
+// function, together with kernels.hip (the scan kernel), is what the measured memory traffic of a workload depends on:
+// bench.py stamps its lines with a hash of exactly these two files and replays profiles/traffic.json only for the same hash.
 #include <algorithm>
 #include <cstdint>
 

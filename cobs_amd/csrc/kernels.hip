@@ -1,233 +1,30 @@
-// cobs_amd/csrc/kernels.hip -- hand-written gfx950 (CDNA4, wave64) kernels of the
-// COBS query path.  Nothing here is translated from the reference: its CPU code
-// gathers rows into a scratch buffer and expands every row BYTE into eight
-// counter lanes through a lookup table (reference cobs/query/classic_search.cpp:
-// 643-1022); at HBM speed that is VALU-bound.  Here each lane owns a 16-byte
-// column chunk (128 documents) of the bit-sliced matrix and keeps the
-// per-document counters bit-sliced as well ("vertical counters"): NP bit planes
-// per 32-bit column word, updated with a Harley-Seal carry-save adder tree, so a
-// gathered row costs ~4.4 VALU ops per 32 documents and the kernel stays on the
-// HBM roofline.
+// cobs_amd/csrc/kernels.hip -- K2 of the COBS query path (gfx950, CDNA4, wave64): row gather + AND over the H hash
+// rows + per-document count (+ optional threshold selection, + optional per-tile top-k)
+//   (read_from_disk, aggregate_rows reference classic_search.cpp:279-307, compute_counts :643-1022, threshold filter of
+//    counts_to_result :127-132).
+// Nothing here is translated from the reference: its CPU code gathers rows into a scratch buffer and expands every row
+// BYTE into eight counter lanes through a lookup table; at HBM speed that is VALU-bound.  Here each lane owns a 16-byte
+// column chunk (128 documents) of the bit-sliced matrix and keeps the per-document counters bit-sliced as well
+// ("vertical counters"): NP bit planes per 32-bit column word, updated with a Harley-Seal carry-save adder tree, so a
+// gathered row costs ~4.4 VALU ops per 32 documents and the kernel stays on the HBM roofline.
 //
-//   K1 hash_kernel    canonicalise + XXH64 + (hash % S_p) per sub-index
-//                     (create_hashes, classic_search.cpp:66-107; canonicalize_kmer,
-//                      util/query.cpp:143-199; modulo at
-//                      classic_index/mmap_search_file.cpp:35 and
-//                      compact_index/mmap_search_file.cpp:58)
-//   K2 scan_kernel    row gather + AND over the H hash rows + per-document count
-//                     (+ optional threshold selection)
-//                     (read_from_disk, aggregate_rows :279-307, compute_counts
-//                      :643-1022, threshold filter of counts_to_result :127-132)
-//   K3 topk_kernel    exact top-k per query (partial_sort of counts_to_result, :134-145)
-//   build_kernel      index construction (classic_index.cpp:40-73): hash terms, set document bits
-//   synth_kernel / repitch_kernel   index staging helpers.
+// The file holds the device code of scan_kernel, its launch templates, and -- as a translation unit of its own -- the
+// plain (FZ = false) instantiations, the LDS-staged ones among them, launch_scan and the scan_* predicates.
+// scan_findere.hip includes it with COBS_SCAN_FINDERE_UNIT defined and instantiates the findere (FZ = true) kernels, so
+// no instantiation exists in both objects.  The device code stays in THIS file because bench.py keys the replay of
+// profiles/traffic.json on a hash of kernels.hip and geometry.cpp: the hash has to see the scan kernel.
+// (K1 is in hash_kernels.hip, K3 in topk_kernels.hip, construction in build_kernels.hip.)
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cstdint>
-#include <cstdlib>
+#include <type_traits>
 
 #include "device_types.hpp"
 #include "kernels.hpp"
-#include "row_table.hpp"     // K1's row-index table: the writer below, K2's reader
-#include "term_hash.hpp"     // rotl64 .. xxh64_view, comp4 / xxh64_31 / canon31, all_acgt / has_newline / set_term_bit
-#include "wave_ops.hpp"      // dpp_mov and its control constants, csa
+#include "row_table.hpp"     // K1's row-index table: K2's reader
+#include "wave_ops.hpp"      // dpp_mov and its control constants, csa, pool_append
 
 namespace cobs_amd {
-
-// ---------------------------------------------------------------------------
-// K1: one thread per query position (canonicalisation and XXH64: term_hash.hpp).
-
-// invalid_bases != 0.  The z characters behind term i's k-mer (`tail`): position i < T - z scores the terms i .. i + z, so it
-// is valid when they hold valid characters too (findere; z = 0: nothing to look at).
-__device__ __forceinline__ bool window_tail_valid(const uint8_t* tail, uint32_t i, uint32_t T, uint32_t z) {
-    if (i + z >= T) return false;               // no window of z + 1 terms starts here: not a scored position
-    uint32_t good = 1u;
-    for (uint32_t s = 0; s < z; ++s) good &= fwd_base(tail[s]) != 0 ? 1u : 0u;
-    return good != 0;
-}
-
-// valid[q] += the lanes of this wave that hold a valid position of query q.  A thread per position of 10 000 reads would be
-// ten million atomics onto ten thousand addresses: the lanes of a wave that share a query (a query's span is a multiple of
-// 8 threads, so a wave sees at most eight) are counted by a ballot first, and one lane adds the sum.  Called by every lane
-// that is still active, with converged control flow.
-__device__ __forceinline__ void add_valid_position(uint32_t* valid, uint32_t q, bool ok) {
-    const uint32_t lane = __lane_id();
-    bool pending = true;
-    for (;;) {
-        const uint64_t waiting = __ballot(pending);
-        if (waiting == 0) break;
-        const uint32_t leader = (uint32_t)__ffsll((unsigned long long)waiting) - 1u;
-        const uint32_t lq = (uint32_t)__shfl((int)q, (int)leader);
-        const bool mine = pending && q == lq;
-        const uint64_t votes = __ballot(mine && ok);
-        if (mine) pending = false;
-        if (lane == leader && votes != 0) atomicAdd(valid + lq, (uint32_t)__popcll(votes));
-    }
-}
-
-// invalid_bases = skip: the thresholds of one file from K1's valid positions, ceil(threshold * V) in double as the host's
-// threshold_for computes it -- and at least 1: a query without a valid position matches nothing, not everything.
-__global__ __launch_bounds__(256) void skip_thresholds_kernel(SkipThresholdArgs a) {
-    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= a.nq) return;
-    const double v = ceil(a.threshold * (double)a.valid[q]);
-    a.thresholds[q] = !(v >= 1.0) ? 1u : v >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)v;
-}
-
-template <typename IdxT>
-__global__ __launch_bounds__(256) void hash_kernel(HashArgs a, uint64_t total_threads) {
-    const uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    // the grid may be larger than the batch needs (a captured launch is replayed for other query lengths)
-    if (gid >= total_threads || gid >= a.span_off[a.nq]) return;
-    // query of this thread: last q with span_off[q] <= gid
-    uint32_t lo = 0, hi = a.nq;
-    while (hi - lo > 1) {
-        uint32_t mid = (lo + hi) >> 1;
-        if (a.span_off[mid] <= gid) lo = mid; else hi = mid;
-    }
-    const uint32_t q = lo;
-    const uint64_t qbase = a.span_off[q];
-    const uint32_t i = (uint32_t)(gid - qbase);
-    const uint32_t len = a.q_len[q];
-    const uint8_t* text = a.text + qbase;
-    const uint32_t k = a.term_size;
-
-    // canonicalize == 1: any character outside ACGT makes the query invalid
-    // (the reference dies, classic_search.cpp:93-96).  Every character of a
-    // query of length >= k lies in some k-mer.
-    // (invalid_bases != 0: such a character only takes the terms that hold it out of the count, below)
-    const bool lenient = a.canonicalize != 0 && a.invalid_bases != 0;
-    if (a.canonicalize != 0 && !lenient && i < len) {
-        if (fwd_base(text[i]) == 0) atomicMax(a.err_query, 0xFFFFFFFFu - q);   // first bad query wins
-    }
-
-    const uint64_t b0 = a.blk_off[q];
-    const uint32_t nblk = (uint32_t)(a.blk_off[q + 1] - b0);
-    const uint32_t T = len - k + 1;
-    // every (query, sub-index) table has nblk blocks of 8 terms plus one all-padding
-    // block that lanes without work in a trip of K2 point at
-    const uint32_t tblk = nblk + 1u;
-    if (i >= tblk * 8u) return;
-    const uint32_t H = a.num_hashes;
-    const uint32_t blk = i >> 3, sub = i & 7u;
-    const RowTableWriter<IdxT> tab(a.table, b0, q, a.npages, H, tblk);
-
-    bool term_ok = true;
-    if (lenient) {
-        if (i < T) {
-            uint32_t good = 1u;
-            for (uint32_t s = 0; s < k; ++s) good &= fwd_base(text[i + s]) != 0 ? 1u : 0u;
-            term_ok = good != 0;
-        }
-        if (a.valid != nullptr) add_valid_position(a.valid, q, i < T && term_ok && window_tail_valid(text + i + k, i, T, a.findere));
-    }
-
-    if (i >= T || !term_ok) {       // padding term (or one that holds an invalid character): the all-zero row of every sub-index
-        for (uint32_t p = 0; p < a.npages; ++p) {
-            const IdxT zr = (IdxT)a.pages[p].sig;
-            for (uint32_t j = 0; j < H; ++j) tab.out(p, blk, j, sub) = zr;
-        }
-        return;
-    }
-
-    KmerView kv{text + i, k, 0u};
-    if (a.canonicalize != 0) {
-        // util/query.cpp:143-199: first strict difference between the forward
-        // base and the complement of the mirrored base decides; the middle base
-        // of an odd k is not compared; ties keep the forward k-mer.
-        uint32_t mode = 1;
-        for (uint32_t s = 0; s < k / 2; ++s) {
-            const int f = (int)fwd_base(text[i + s]);
-            const int r = (int)rev_base(text[i + k - 1 - s]);
-            if (f < r) break;
-            if (f > r) { mode = 2; break; }
-        }
-        kv.mode = mode;
-    }
-    for (uint32_t j = 0; j < H; ++j) {
-        const uint64_t h = xxh64_view(kv, (uint64_t)j);
-        for (uint32_t p = 0; p < a.npages; ++p) {
-            const PageDev pg = a.pages[p];
-            tab.out(p, blk, j, sub) = (IdxT)fast_mod(h, pg.sig, pg.magic);
-        }
-    }
-}
-
-// K1 specialised for k = 31 (the COBS default): the 31-mer lives in eight 32-bit
-// registers, complement and reversal are done four bases at a time, and the
-// reference's comparison of the first 15 positions (util/query.cpp:155-190) becomes
-// a big-endian integer comparison of forward vs reverse complement (canon31, term_hash.hpp).
-template <typename IdxT>
-__global__ __launch_bounds__(256) void hash_kernel_k31(HashArgs a, uint64_t total_threads) {
-    const uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (gid >= total_threads || gid >= a.span_off[a.nq]) return;
-    uint32_t lo = 0, hi = a.nq;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (a.span_off[mid] <= gid) lo = mid; else hi = mid;
-    }
-    const uint32_t q = lo;
-    const uint64_t qbase = a.span_off[q];
-    const uint32_t i = (uint32_t)(gid - qbase);
-    const uint32_t len = a.q_len[q];
-    const uint8_t* text = a.text + qbase;
-    const bool lenient = a.canonicalize != 0 && a.invalid_bases != 0;
-    if (a.canonicalize != 0 && !lenient && i < len) {
-        if (fwd_base(text[i]) == 0) atomicMax(a.err_query, 0xFFFFFFFFu - q);   // first bad query wins
-    }
-    const uint64_t b0 = a.blk_off[q];
-    const uint32_t nblk = (uint32_t)(a.blk_off[q + 1] - b0);
-    const uint32_t T = len - 31u + 1u;
-    const uint32_t tblk = nblk + 1u;
-    if (i >= tblk * 8u) return;
-    const uint32_t H = a.num_hashes;
-    const uint32_t blk = i >> 3, sub = i & 7u;
-    const RowTableWriter<IdxT> tab(a.table, b0, q, a.npages, H, tblk);
-    // the k-mer and one following byte as 8 (unaligned) dwords; the text buffer is padded
-    uint32_t f[8];
-    if (i < T) {
-        const uint8_t* p = text + i;
-        const uint32_t mis = (uint32_t)((uintptr_t)p & 3u);
-        const uint32_t* w = reinterpret_cast<const uint32_t*>(p - mis);
-        uint32_t r[9];
-#pragma unroll
-        for (int j = 0; j < 9; ++j) r[j] = w[j];
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-            f[j] = mis == 0 ? r[j] : (uint32_t)(((uint64_t)r[j] | ((uint64_t)r[j + 1] << 32)) >> (8 * mis));
-        f[7] &= 0x00FFFFFFu;                      // byte 31 is not part of the 31-mer
-    }
-    bool term_ok = true;
-    if (lenient) {
-        if (i < T) {
-            // (the masked top byte of f[7] stands in as an 'A': the character behind the k-mer does not decide on it)
-            bool good = all_acgt(f[7] | 0x41000000u);
-#pragma unroll
-            for (int j = 0; j < 7; ++j) good = good && all_acgt(f[j]);
-            term_ok = good;
-        }
-        if (a.valid != nullptr) add_valid_position(a.valid, q, i < T && term_ok && window_tail_valid(text + i + 31u, i, T, a.findere));
-    }
-    if (i >= T || !term_ok) {
-        for (uint32_t p = 0; p < a.npages; ++p) {
-            const IdxT zr = (IdxT)a.pages[p].sig;
-            for (uint32_t j = 0; j < H; ++j) tab.out(p, blk, j, sub) = zr;
-        }
-        return;
-    }
-    uint32_t c[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) c[j] = f[j];
-    if (a.canonicalize != 0) canon31(f, c);
-    for (uint32_t j = 0; j < H; ++j) {
-        const uint64_t h = xxh64_31(c, (uint64_t)j);
-        for (uint32_t p = 0; p < a.npages; ++p) {
-            const PageDev pg = a.pages[p];
-            tab.out(p, blk, j, sub) = (IdxT)fast_mod(h, pg.sig, pg.magic);
-        }
-    }
-}
 
 // ---------------------------------------------------------------------------
 // K2: gather + AND + bit-sliced count.
@@ -541,17 +338,6 @@ __device__ __forceinline__ uint32_t group_incl_scan(uint32_t v, uint32_t W, uint
     return v;
 }
 
-// inclusive prefix sum over the 64 lanes of a wave: four row steps, then lane 15 / lane 31 broadcasts (GFX9 DPP)
-__device__ __forceinline__ uint32_t wave_incl_scan_dpp(uint32_t v) {
-    v += dpp_mov<kDppRowShr + 1>(v);
-    v += dpp_mov<kDppRowShr + 2>(v);
-    v += dpp_mov<kDppRowShr + 4>(v);
-    v += dpp_mov<kDppRowShr + 8>(v);
-    v += dpp_mov<kDppBcast15, 0xA, 0xF, false>(v);      // rows 1 and 3 += the total of the row before
-    v += dpp_mov<kDppBcast31, 0xC, 0xF, false>(v);      // rows 2 and 3 += the total of the first half
-    return v;
-}
-
 // Exact top-k of ONE tile, straight from the bit-sliced counters (run_topk without score rows): the k best
 // documents of a tile under (score desc, document asc) are a superset of the tile's share of the query's k
 // best (counts_to_result's partial_sort, classic_search.cpp:134-145), so K3 only has to merge tiles x k
@@ -649,6 +435,14 @@ __device__ __forceinline__ void tile_topk(const ScanArgs& a, const uint32_t (&pl
     }
 }
 
+// scan_kernel is ONE body on purpose.  Its stages were tried as __device__ __forceinline__ functions (the tile setup as a
+// struct, the trip count, the findere priming, each row loop, the two merges, each epilogue) and every one of them moved
+// the compiler's schedule: the row loops cost scan_kernel<8, 1, false, u8, false, u32> 29 spills (116 -> 128 VGPRs) and
+// its findere twin a wave per SIMD; the tile struct moved AGPRs in <20|24|32, 4, false, u32, false, u32, false, false,
+// true> and took <10, 1, true, u16, false, u32, false, true, true> from 136 to 138 VGPRs; the epilogues added 55
+// instructions to the four-wave multi-query kernels; the LDS-staged loop lost 47.  With all of them inline the code
+// object is instruction for instruction the one of the single-file version (profiles/scan_split_isa_diff.txt).  Only
+// the hit pool's append (pool_append, wave_ops.hpp) is shared: it compiles to the same instructions.
 // MQ ("multi-query", short queries): the G = 64 / W lane groups of a wave belong to G
 // DIFFERENT queries (q = qi*G + grp) instead of splitting one query's blocks.  Every lane
 // group then walks all blocks of its own query (divided over the NW waves only): G times
@@ -1117,13 +911,7 @@ __global__ __launch_bounds__(NW * 64, (!FZ && ((TK && H1) || (!H1 && sizeof(IdxT
                         }
                     }
                     if (__any(mask != 0u)) {
-                        const uint32_t n = __popc(mask);
-                        const uint32_t incl = wave_incl_scan_dpp(n);
-                        const uint32_t total = __shfl(incl, 63);
-                        unsigned long long base = 0ull;
-                        if (lane == 63u) base = atomicAdd(a.hit_count, (unsigned long long)total);
-                        base = __shfl(base, 63);
-                        unsigned long long pos = base + incl - n;
+                        unsigned long long pos = pool_append((uint32_t)__popc(mask), a.hit_count, lane);
                         while (mask != 0u) {
                             const uint32_t d = (uint32_t)__ffs((int)mask) - 1u;
                             mask &= mask - 1u;
@@ -1181,13 +969,7 @@ __global__ __launch_bounds__(NW * 64, (!FZ && ((TK && H1) || (!H1 && sizeof(IdxT
             if (nd < 32u) ge &= nd == 0u ? 0u : (1u << nd) - 1u;
             if (!valid) ge = 0u;
             if (__any(ge != 0u)) {
-                const uint32_t n = __popc(ge);
-                const uint32_t incl = wave_incl_scan_dpp(n);
-                const uint32_t total = __shfl(incl, 63);
-                unsigned long long base = 0ull;
-                if (lane == 63u) base = atomicAdd(a.hit_count, (unsigned long long)total);
-                base = __shfl(base, 63);
-                unsigned long long pos = base + incl - n;
+                unsigned long long pos = pool_append((uint32_t)__popc(ge), a.hit_count, lane);
                 while (ge != 0u) {
                     const uint32_t d = (uint32_t)__ffs((int)ge) - 1u;
                     ge &= ge - 1u;
@@ -1284,13 +1066,7 @@ __global__ __launch_bounds__(NW * 64, (!FZ && ((TK && H1) || (!H1 && sizeof(IdxT
                     if (cnt[d] >= thr && doc + d < a.num_docs) mask |= 1u << d;
             }
             if (__any(mask != 0u)) {
-                const uint32_t n = __popc(mask);
-                const uint32_t incl = wave_incl_scan_dpp(n);
-                const uint32_t total = __shfl(incl, 63);
-                unsigned long long base = 0ull;
-                if (lane == 63u) base = atomicAdd(a.hit_count, (unsigned long long)total);
-                base = __shfl(base, 63);
-                unsigned long long pos = base + incl - n;
+                unsigned long long pos = pool_append((uint32_t)__popc(mask), a.hit_count, lane);
 #pragma unroll
                 for (int d = 0; d < 8; ++d) {
                     if (mask & (1u << d)) {
@@ -1305,647 +1081,12 @@ __global__ __launch_bounds__(NW * 64, (!FZ && ((TK && H1) || (!H1 && sizeof(IdxT
 }
 
 // ---------------------------------------------------------------------------
-// K3: exact top-k selection per query (the device side of counts_to_result's
-// partial_sort, reference classic_search.cpp:127-145, for all three Score widths of
-// :453-504): find the score s* of the k-th best document with a radix descent over the
-// score bits (histogram levels of at most 12 bits each: one level for 8/10/12-bit scores,
-// two up to 24 bits, three for 32-bit scores), emit every document with score > s* and, in
-// ascending document order, as many documents with score == s* as are still needed, then
-// order the <= k survivors by (score desc, document asc) in LDS (bitonic sort on
-// (~score, doc) keys) -- the host copies the result as is.
-// One work-group (4 waves) per query; wave w owns the contiguous quarter w of the
-// documents so that ballot prefixes keep document order.
-
-__device__ __forceinline__ uint32_t wave_prefix(unsigned long long mask, uint32_t lane) {
-    return (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-}
-
-__device__ __forceinline__ uint32_t wave_excl_scan(uint32_t v, uint32_t lane, uint32_t* total) {
-    uint32_t incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t t = __shfl_up(incl, off);
-        if (lane >= (uint32_t)off) incl += t;
-    }
-    *total = __shfl(incl, 63);
-    return incl - v;
-}
-
-// eight consecutive scores (u8, u16 or u32) starting at document i (a multiple of 8)
-template <typename ST>
-__device__ __forceinline__ void load_scores8(const ST* row, uint32_t i, uint32_t (&s)[8]) {
-    if constexpr (sizeof(ST) == 1) {
-        const uint2 v = *reinterpret_cast<const uint2*>(row + i);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) s[j] = ((j < 4 ? v.x : v.y) >> ((j & 3) * 8)) & 0xFFu;
-    } else if constexpr (sizeof(ST) == 2) {
-        const uint4 v = *reinterpret_cast<const uint4*>(row + i);
-        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int j = 0; j < 8; ++j) s[j] = (w[j >> 1] >> ((j & 1) * 16)) & 0xFFFFu;
-    } else {
-        const uint4 a = *reinterpret_cast<const uint4*>(row + i);
-        const uint4 b = *reinterpret_cast<const uint4*>(row + i + 4);
-        s[0] = a.x; s[1] = a.y; s[2] = a.z; s[3] = a.w;
-        s[4] = b.x; s[5] = b.y; s[6] = b.z; s[7] = b.w;
-    }
-}
-
-// Dynamic LDS: hist[4 waves][NB] (NB = 2^level_bits <= 4096; reused by every level and, after
-// the emission, as the sort buffer: 8192 eight-byte keys) | partial[256] | sh[16]
-// POOL: the input is not a score row but the candidate pool of run_topk without score rows (K2's tile_topk):
-// nslots (document, score) entries per query in ascending document order, unused ones marked with
-// document 0xFFFFFFFF; the same selection and ordering over tiles x k candidates.
-template <typename ST, bool POOL>
-__device__ __forceinline__ void load_elems8(const void* rowp, uint32_t i, uint32_t w1, uint32_t doc_base, uint32_t thr,
-                                            uint32_t (&s)[8], uint32_t (&d)[8], uint32_t& okmask) {
-    okmask = 0u;
-    if constexpr (POOL) {
-        const uint4* e = reinterpret_cast<const uint4*>(reinterpret_cast<const uint2*>(rowp) + i);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            uint4 v = make_uint4(0xFFFFFFFFu, 0u, 0xFFFFFFFFu, 0u);
-            if (i + 2 * j < w1) v = e[j];            // two entries per load; the row is padded to 8 entries, i is a multiple of 8
-            d[2 * j] = v.x; s[2 * j] = v.y; d[2 * j + 1] = v.z; s[2 * j + 1] = v.w;
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-            if (i + j < w1 && d[j] != 0xFFFFFFFFu && s[j] >= thr) okmask |= 1u << j;
-    } else {
-        load_scores8<ST>(reinterpret_cast<const ST*>(rowp), i, s);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            d[j] = doc_base + i + j;
-            if (i + j < w1 && s[j] >= thr) okmask |= 1u << j;
-        }
-    }
-}
-
-template <typename ST, bool POOL = false>
-__global__ __launch_bounds__(256) void topk_kernel(TopkArgs a) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    const uint32_t NB = 1u << a.level_bits;
-    uint32_t* hist = reinterpret_cast<uint32_t*>(smem);
-    uint32_t* partial = hist + 4u * NB;
-    uint32_t* sh = partial + 256;
-    const uint32_t q = blockIdx.x;
-    const uint32_t tid = threadIdx.x, lane = tid & 63u;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const void* row = POOL ? (const void*)(reinterpret_cast<const uint2*>(a.counts) + (uint64_t)q * a.counts_stride)
-                           : (const void*)(reinterpret_cast<const ST*>(a.counts) + (uint64_t)q * a.counts_stride + a.counts_offset);
-    const uint32_t thr = a.thresholds ? a.thresholds[q] : 0u;
-    uint32_t n = a.nslots;                       // real documents among the local slots (POOL: pool entries)
-    if constexpr (!POOL) {
-        if (a.doc_base >= a.num_docs) n = 0;
-        else if (a.num_docs - a.doc_base < n) n = a.num_docs - a.doc_base;
-    }
-    const uint32_t k = a.k;
-    // wave w owns the contiguous document range [w0, w1); 512 documents per iteration
-    const uint32_t per = ((n + 3u) / 4u + 511u) / 512u * 512u;
-    const uint32_t w0 = wave * per < n ? wave * per : n;
-    const uint32_t w1 = w0 + per < n ? w0 + per : n;
-
-    // ---- radix descent: after level l the top (l+1)*level_bits bits of s* are known
-    uint32_t prefix = 0, n_above = 0, take_all = 0;
-    uint32_t bits_left = a.score_bits;           // bits below the known prefix
-    uint32_t* myh = hist + wave * NB;
-    for (uint32_t level = 0; level < a.levels; ++level) {
-        const uint32_t lb = bits_left < a.level_bits ? bits_left : a.level_bits;     // bits of this level
-        const uint32_t shift = bits_left - lb;
-        const uint32_t nb = 1u << lb, mask = nb - 1u;
-        for (uint32_t i = tid; i < 4u * NB; i += 256) hist[i] = 0;
-        __syncthreads();
-        for (uint32_t i0 = w0; i0 < w1; i0 += 512) {
-            const uint32_t i = i0 + lane * 8u;
-            if (i < w1) {
-                uint32_t sc[8], dc[8], ok;
-                load_elems8<ST, POOL>(row, i, w1, a.doc_base, thr, sc, dc, ok);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const uint32_t s = sc[j];
-                    // the bits above this level must equal the prefix found so far
-                    const bool in = level == 0 || (bits_left >= 32u ? true : (s >> bits_left) == prefix);
-                    if ((ok >> j & 1u) && in) atomicAdd(&myh[(s >> shift) & mask], 1u);
-                }
-            }
-        }
-        __syncthreads();
-        {   // parallel search of the bin holding the k-th best: per-thread segment sums, then thread 0
-            const uint32_t seg = (nb + 255u) / 256u;
-            uint32_t sum = 0;
-            for (uint32_t b = tid * seg; b < (tid + 1) * seg && b < nb; ++b)
-                sum += hist[b] + hist[NB + b] + hist[2 * NB + b] + hist[3 * NB + b];
-            partial[tid] = sum;
-            __syncthreads();
-            if (tid == 0) {
-                uint32_t above = n_above;
-                int t = 255;
-                for (; t >= 0; --t) {
-                    if (above + partial[t] >= k) break;
-                    above += partial[t];
-                }
-                int hb = -1;
-                if (t >= 0) {
-                    int b = (int)((uint32_t)(t + 1) * seg) - 1;
-                    if (b >= (int)nb) b = (int)nb - 1;
-                    for (; b >= (int)((uint32_t)t * seg); --b) {
-                        const uint32_t c = hist[b] + hist[NB + b] + hist[2 * NB + b] + hist[3 * NB + b];
-                        if (above + c >= k) { hb = b; break; }
-                        above += c;
-                    }
-                }
-                sh[0] = hb < 0 ? 0u : (uint32_t)hb;
-                sh[1] = above;
-                sh[2] = hb < 0 ? 1u : 0u;        // fewer than k passing documents: take them all
-            }
-            __syncthreads();
-        }
-        const uint32_t hb = sh[0];
-        n_above = sh[1];
-        take_all = sh[2];
-        prefix = (lb >= 32u ? 0u : (prefix << lb)) | hb;
-        bits_left = shift;
-        if (take_all) break;                     // only possible at level 0 (block-uniform)
-        if (level + 1 < a.levels) __syncthreads();        // hist is zeroed again
-    }
-    uint32_t cut = take_all ? thr : prefix;
-    // ties: documents with score == cut, per wave (the last level's per-wave histogram bins)
-    uint32_t eq_base = 0, eq_total = 0;
-    if (!take_all) {
-        const uint32_t lastbits = a.score_bits - (a.levels - 1u) * a.level_bits;
-        const uint32_t bin = cut & ((lastbits >= 32u ? 0u : (1u << lastbits)) - 1u);
-        for (uint32_t w = 0; w < 4; ++w) {
-            const uint32_t c = hist[w * NB + bin];
-            if (w < wave) eq_base += c;
-            eq_total += c;
-        }
-    }
-    const uint32_t need_eq = take_all ? 0u : k - n_above;
-    if (tid == 0) sh[5] = 0;                      // emission cursor of the documents above the cut
-    __syncthreads();
-    // ---- emission
-    uint2* out = a.out + (uint64_t)q * (a.out_stride ? a.out_stride : k);
-    for (uint32_t i0 = w0; i0 < w1; i0 += 512) {
-        const uint32_t i = i0 + lane * 8u;
-        uint32_t s8[8], d8[8];
-        uint32_t gt = 0, eq = 0;
-        if (i < w1) {
-            uint32_t ok;
-            load_elems8<ST, POOL>(row, i, w1, a.doc_base, thr, s8, d8, ok);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const uint32_t s = s8[j];
-                const bool pass = (ok >> j & 1u) != 0u;
-                if (pass && (take_all || s > cut)) gt |= 1u << j;
-                if (pass && !take_all && s == cut) eq |= 1u << j;
-            }
-        }
-        if (__any(gt != 0u)) {
-            uint32_t total;
-            const uint32_t excl = wave_excl_scan((uint32_t)__popc(gt), lane, &total);
-            uint32_t base = 0;
-            if (lane == 63u) base = atomicAdd(&sh[5], total);
-            base = __shfl(base, 63);
-            uint32_t pos = base + excl;
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-                if (gt & (1u << j)) out[pos++] = make_uint2(d8[j], s8[j]);
-        }
-        if (__any(eq != 0u)) {
-            uint32_t total;
-            const uint32_t excl = wave_excl_scan((uint32_t)__popc(eq), lane, &total);
-            uint32_t r = eq_base + excl;
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-                if (eq & (1u << j)) {
-                    if (r < need_eq) out[n_above + r] = make_uint2(d8[j], s8[j]);
-                    ++r;
-                }
-            eq_base += total;
-        }
-    }
-    __syncthreads();
-    const uint32_t cnt = take_all ? sh[5] : n_above + (eq_total < need_eq ? eq_total : need_eq);
-    if (tid == 0 && a.out_count) a.out_count[q] = cnt;
-    // (one tile of the candidate pool: what the survivors leave of its k entries is marked unused, as tile_topk does)
-    if (a.pad_out)
-        for (uint32_t i = cnt + tid; i < k; i += 256) out[i] = make_uint2(0xFFFFFFFFu, 0u);
-    // ---- order the survivors: (score desc, doc asc) = ascending (~score << 32 | doc)
-    if (a.sort_limit && cnt > 1u && cnt <= a.sort_limit) {      // block-uniform condition
-        __syncthreads();                          // everybody has read sh[]: the key area may overlap it
-        unsigned long long* key = reinterpret_cast<unsigned long long*>(smem);
-        uint32_t m = 2;
-        while (m < cnt) m <<= 1;
-        for (uint32_t i = tid; i < m; i += 256) {
-            unsigned long long kv = ~0ull;        // padding sorts last
-            if (i < cnt) {
-                const uint2 e = out[i];
-                kv = ((unsigned long long)(~e.y) << 32) | e.x;
-            }
-            key[i] = kv;
-        }
-        __syncthreads();
-        for (uint32_t size = 2; size <= m; size <<= 1) {
-            for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
-                for (uint32_t t = tid; t < (m >> 1); t += 256) {
-                    const uint32_t lo = (t / stride) * (stride << 1) + (t % stride), hi = lo + stride;
-                    const bool up = ((lo & size) == 0u);
-                    const unsigned long long x = key[lo], y = key[hi];
-                    if ((x > y) == up) { key[lo] = y; key[hi] = x; }
-                }
-                __syncthreads();
-            }
-        }
-        for (uint32_t i = tid; i < cnt; i += 256) {
-            const unsigned long long kv = key[i];
-            out[i] = make_uint2((uint32_t)kv, ~(uint32_t)(kv >> 32));
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------
-// The threshold filter over ACCUMULATED scores (reference classic_search.cpp:127-132).  A streamed sub-index that is
-// larger than a stream buffer is counted row range by row range (pass.cpp): K2 sees partial counts there and cannot
-// compare them with a threshold.  Its ranges add up in a scratch matrix of the sub-index's own width (no score rows of
-// the whole index), and after the last range this kernel does what K2's epilogue does for a sub-index it sees whole:
-// score >= threshold over real documents -> (query, file, document, score) records into the batch's hit pool, one
-// wave-aggregated atomic per wave.  One thread per (query, 8 consecutive slots).
-template <typename ST>
-__global__ __launch_bounds__(256) void select_rows_kernel(SelectRowsArgs a) {
-    const uint32_t groups = (a.nslots + 7u) / 8u;
-    const uint64_t gid = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t qq = gid / groups;
-    const bool live = qq < a.nq;                      // (no early return: the scan below runs over whole waves)
-    const uint32_t q = live ? (uint32_t)qq : 0u;
-    const uint32_t i = (uint32_t)(gid - qq * groups) * 8u;
-    uint32_t s8[8];
-    uint32_t mask = 0u;
-    if (live) {
-        load_scores8<ST>(reinterpret_cast<const ST*>(a.scores) + (uint64_t)q * a.stride, i, s8);
-        const uint32_t thr = a.thresholds[q];
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-            if (i + j < a.nslots && a.doc0 + i + j < a.num_docs && s8[j] >= thr) mask |= 1u << j;
-    }
-    if (__any(mask != 0u)) {
-        const uint32_t n = (uint32_t)__popc(mask);
-        const uint32_t incl = wave_incl_scan_dpp(n);
-        const uint32_t total = __shfl(incl, 63);
-        unsigned long long base = 0ull;
-        if (lane == 63u) base = atomicAdd(a.hit_count, (unsigned long long)total);
-        base = __shfl(base, 63);
-        unsigned long long pos = base + incl - n;
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-            if (mask & (1u << j)) {
-                if (pos < a.hit_cap) a.hits[pos] = HitDev{q, a.part, a.doc0 + i + (uint32_t)j, s8[j]};
-                ++pos;
-            }
-    }
-}
-
-// ---------------------------------------------------------------------------
-// Construction: the reference sets bit (doc % 8) of byte doc / 8
-// of row XXH64(canon(term), seed j) % signature_size for every term of every document
-// (cobs/construction/classic_index.cpp:40-73).  One thread per position of the term text; the
-// text is a sequence of stretches (documents.hpp): in a raw stretch every k-gram is a term, in a
-// line stretch a position starts a term if the next k characters hold no '\n'.  With
-// canonicalize = 1 the reference hashes the canonicalised buffer even when it holds invalid
-// characters (mapped to 0), which the generic byte view reproduces; 31-mers of valid bases --
-// nearly all of a DNA collection -- take the register path of the query hash kernel instead
-// (unaligned dword loads, canon31, unrolled XXH64).  set_term_bit (term_hash.hpp) is where a bit goes.
-
-// One thread per (four consecutive rows, one 32-document word of the matrix row): reads the rows'
-// bytes from every plane whose column falls into the word (dword loads, coalesced across the
-// rows of a wave), ORs the bits into the four words.  Launches of one build are ordered on one
-// stream and every (row, word) belongs to one thread, so the read-modify-write needs no atomic.
-__global__ __launch_bounds__(256) void pack_bytemap_kernel(PackArgs a) {
-    const uint32_t w0 = a.col_base >> 5, w1 = (a.col_base + a.ndocs - 1u) >> 5;      // words the launch touches
-    const uint64_t nquads = (a.rows + 3u) / 4u;
-    const uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const uint64_t quad = gid % nquads;                   // consecutive threads = consecutive rows
-    const uint32_t w = w0 + (uint32_t)(gid / nquads);
-    if (w > w1) return;
-    const uint64_t r0 = quad * 4u;
-    const uint32_t c0 = max(a.col_base, w << 5), c1 = min(a.col_base + a.ndocs, (w + 1u) << 5);
-    uint32_t acc[4] = {0u, 0u, 0u, 0u};
-    for (uint32_t c = c0; c < c1; ++c) {
-        const uint32_t x = *reinterpret_cast<const uint32_t*>(a.bytemap + (uint64_t)(c - a.col_base) * a.bm_stride + r0);
-        const uint32_t b = c & 31u;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) acc[i] |= ((x >> (8 * i)) & 1u) << b;
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        if (r0 + i < a.rows && acc[i] != 0u) {
-            uint32_t* m = a.matrix + ((r0 + i) * a.row_bytes) / 4u + w;
-            *m |= acc[i];
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void build_kernel(BuildArgs a, uint64_t total_bytes) {
-    // the stretch of the block's first position (wave-uniform search), then a few steps per thread
-    const uint64_t base = (uint64_t)blockIdx.x * 256u;
-    uint32_t lo = 0, hi = a.nsegs;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (a.seg_off[mid] <= base) lo = mid; else hi = mid;
-    }
-    const uint64_t gid = base + threadIdx.x;
-    if (gid >= total_bytes) return;
-    while (a.seg_off[lo + 1] <= gid) ++lo;            // seg_off[nsegs] = total_bytes > gid
-    const uint32_t k = a.term_size;
-    if (gid + k > a.seg_off[lo + 1]) return;          // the term would leave its stretch
-    const uint32_t colw = a.seg_col[lo];
-    if (colw == kBuildGapStretch) return;
-    const bool raw = (colw & kBuildRawStretch) != 0u;
-    const uint32_t doc = colw & ~kBuildRawStretch;
-    const uint8_t* p = a.text + gid;
-    if (k == 31u) {
-        // the 31-mer and one following byte as 8 (unaligned) dwords; the text buffer is padded
-        uint32_t f[8];
-        {
-            const uint32_t mis = (uint32_t)((uintptr_t)p & 3u);
-            const uint32_t* w = reinterpret_cast<const uint32_t*>(p - mis);
-            uint32_t r[9];
-#pragma unroll
-            for (int j = 0; j < 9; ++j) r[j] = w[j];
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-                f[j] = mis == 0 ? r[j] : (uint32_t)(((uint64_t)r[j] | ((uint64_t)r[j + 1] << 32)) >> (8 * mis));
-        }
-        f[7] &= 0x00FFFFFFu;
-        if (!raw) {
-            bool nl = false;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) nl |= has_newline(f[j]);
-            if (nl) return;                           // the term would span a sequence boundary
-        }
-        bool fast = true;
-        uint32_t c[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) c[j] = f[j];
-        if (a.canonicalize != 0) {
-#pragma unroll
-            for (int j = 0; j < 7; ++j) fast &= all_acgt(f[j]);
-            fast &= all_acgt(f[7] | 0x41000000u);
-            if (fast) canon31(f, c);
-        }
-        if (fast) {
-            for (uint32_t j = 0; j < a.num_hashes; ++j) {
-                const uint64_t row = fast_mod(xxh64_31(c, (uint64_t)j), a.signature_size, a.magic);
-                set_term_bit(a, doc, row);
-            }
-            return;
-        }
-    } else if (!raw) {
-        for (uint32_t i = 0; i < k; ++i)
-            if (p[i] == '\n') return;                 // the term would span a sequence boundary
-    }
-    KmerView kv{p, k, 0u};
-    if (a.canonicalize != 0) {
-        uint32_t mode = 1;
-        for (uint32_t s = 0; s < k / 2; ++s) {
-            const int f = (int)fwd_base(p[s]);
-            const int r = (int)rev_base(p[k - 1 - s]);
-            if (f < r) break;
-            if (f > r) { mode = 2; break; }
-        }
-        kv.mode = mode;
-    }
-    for (uint32_t j = 0; j < a.num_hashes; ++j) {
-        const uint64_t row = fast_mod(xxh64_view(kv, (uint64_t)j), a.signature_size, a.magic);
-        set_term_bit(a, doc, row);
-    }
-}
-
-// ---------------------------------------------------------------------------
-// procedural index bits (same definition as the checker's generator)
-
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {
-    z += 0x9E3779B97F4A7C15ULL;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    return z ^ (z >> 31);
-}
-
-// classic_construct_random (construction/classic_index.cpp:661-725): every document is
-// document_size random 31-mers; each is canonicalised, hashed and its bit set.  One thread per
-// (document, k-mer); the 31 bases are the low 62 bits of mix64(mix64(seed ^ doc) + j), two bits
-// per base (A C G T), first base in the lowest bits.
-__global__ __launch_bounds__(256) void random_build_kernel(RandomBuildArgs a, uint64_t total) {
-    const uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (gid >= total) return;
-    const uint64_t doc = gid / a.document_size, j = gid - doc * a.document_size;
-    uint64_t bits = mix64(mix64(a.seed ^ (a.doc0 + doc)) + j);
-    uint32_t f[8];
-#pragma unroll
-    for (int w = 0; w < 8; ++w) {
-        uint32_t v = 0;
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            const uint32_t code = (uint32_t)(bits >> (2 * (4 * w + b))) & 3u;
-            // A 0x41, C 0x43, G 0x47, T 0x54
-            const uint32_t ch = code == 0 ? 0x41u : code == 1 ? 0x43u : code == 2 ? 0x47u : 0x54u;
-            v |= ch << (8 * b);
-        }
-        f[w] = v;
-    }
-    f[7] &= 0x00FFFFFFu;
-    uint32_t c[8];
-#pragma unroll
-    for (int w = 0; w < 8; ++w) c[w] = f[w];
-    canon31(f, c);
-    const uint64_t col = a.doc0 + doc;
-    const uint64_t byte_in_row = col >> 3;
-    const uint32_t bit = 1u << ((uint32_t)(byte_in_row & 3u) * 8u + (uint32_t)(col & 7u));
-    for (uint32_t h = 0; h < a.num_hashes; ++h) {
-        const uint64_t row = fast_mod(xxh64_31(c, (uint64_t)h), a.signature_size, a.magic);
-        atomicOr(a.matrix + (row * a.row_bytes + byte_in_row) / 4u, bit);
-    }
-}
-
-// classic_combine (construction/classic_index.cpp:195-327): row r of the output is the rows r of
-// the inputs concatenated at BIT granularity (input i contributes its row_bits[i] documents).
-// One thread per output byte.
-__global__ __launch_bounds__(256) void combine_kernel(CombineArgs a) {
-    const uint64_t total = a.rows * a.dst_row_bytes;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-         i += (uint64_t)gridDim.x * blockDim.x) {
-        const uint64_t row = i / a.dst_row_bytes;
-        const uint64_t ob = i - row * a.dst_row_bytes;
-        uint64_t bit = ob * 8;                                  // first output document of this byte
-        // source holding document `bit`: last s with bit_off[s] <= bit
-        uint32_t lo = 0, hi = a.nsrc;
-        while (hi - lo > 1) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (a.bit_off[mid] <= bit) lo = mid; else hi = mid;
-        }
-        uint32_t sidx = lo, v = 0;
-#pragma unroll 1
-        for (uint32_t b = 0; b < 8 && bit < a.bit_off[a.nsrc]; ++b, ++bit) {
-            while (bit >= a.bit_off[sidx + 1]) ++sidx;          // sources without documents are skipped
-            const uint64_t sb = bit - a.bit_off[sidx];
-            const uint8_t byte = a.src[sidx][row * a.src_row_bytes[sidx] + (sb >> 3)];
-            v |= ((uint32_t)(byte >> (sb & 7u)) & 1u) << b;
-        }
-        a.dst[i] = (uint8_t)v;
-    }
-}
-
-__device__ __forceinline__ uint64_t synth_word(uint64_t seed, uint32_t page, uint64_t row, uint64_t w) {
-    const uint64_t key = mix64(seed ^ mix64(((uint64_t)page << 40) ^ row));
-    const uint64_t c = key + w * 6;
-    const uint64_t x = mix64(c) & mix64(c + 1);
-    const uint64_t y = mix64(c + 2) & mix64(c + 3) & mix64(c + 4) & mix64(c + 5);
-    return x | y;
-}
-
-// grid: blockIdx.y = local page, grid-stride over (row, 8-byte word) of that page
-__global__ __launch_bounds__(256) void synth_kernel(SynthArgs a) {
-    const uint32_t p = blockIdx.y;
-    const PageDev pd = a.pages[p];
-    const uint32_t wpr = a.pitch / 8u;                    // words per HBM row
-    const uint64_t nwords = (pd.sig + 1) * (uint64_t)wpr; // incl. the zero row
-    const uint32_t fpage = a.first_page + p;
-    const uint64_t first_doc = (uint64_t)fpage * a.page_docs;
-    const uint64_t live = a.num_docs > first_doc ? a.num_docs - first_doc : 0;   // real documents of the page
-    uint64_t* dst = reinterpret_cast<uint64_t*>(a.blob + pd.base);
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nwords;
-         i += (uint64_t)gridDim.x * blockDim.x) {
-        const uint64_t row = i / wpr;
-        const uint32_t w = (uint32_t)(i - row * wpr);
-        uint64_t v = 0;
-        if (row < pd.sig) {
-            const uint64_t fb = a.col0 + (uint64_t)w * 8u;     // file-level byte of this word
-            // local bytes beyond valid_bytes and file bytes beyond the row are zero
-            const uint64_t gw = fb >> 3;
-            uint64_t x = synth_word(a.seed, fpage, row, gw);
-            if ((fb & 7u) != 0) {      // column shard not 8-byte aligned: stitch two words
-                const uint64_t x2 = synth_word(a.seed, fpage, row, gw + 1);
-                const uint32_t s = (uint32_t)(fb & 7u) * 8u;
-                x = (x >> s) | (x2 << (64 - s));
-            }
-#pragma unroll
-            for (uint32_t b = 0; b < 8; ++b) {
-                const uint64_t lb = (uint64_t)w * 8u + b;      // local byte
-                const uint64_t gb = fb + b;                    // file-level byte
-                uint32_t byte = (uint32_t)(x >> (8 * b)) & 0xFFu;
-                if (lb >= pd.valid_bytes || gb >= a.row_bytes || gb * 8 >= live) byte = 0;
-                else if (gb * 8 + 8 > live) byte &= (1u << (uint32_t)(live - gb * 8)) - 1u;
-                v |= (uint64_t)byte << (8 * b);
-            }
-        }
-        dst[i] = v;
-    }
-}
-
-// cobs_gpu_plant: one thread per term of the text.  Document i holds term t iff mix64(salt ^ doc << 32 ^ t) % 1000 <
-// keep_permille (the test suite's checker restates this rule); a held term sets, for each of its H hashes, bit doc % 8
-// of byte doc / 8 of row hash % S_p -- what classic_index.cpp:40-73 does for a document's own terms.
-__global__ __launch_bounds__(256) void plant_kernel(PlantArgs a) {
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t k = a.term_size;
-    if (a.len < k || t > a.len - k) return;
-    const uint8_t* text = a.text + t;
-    KmerView kv{text, k, 0u};
-    if (a.canonicalize != 0) {
-        for (uint32_t s = 0; s < k; ++s)
-            if (fwd_base(text[s]) == 0) { *a.bad = 1u; return; }
-        uint32_t mode = 1;
-        for (uint32_t s = 0; s < k / 2; ++s) {
-            const int f = (int)fwd_base(text[s]);
-            const int r = (int)rev_base(text[k - 1 - s]);
-            if (f < r) break;
-            if (f > r) { mode = 2; break; }
-        }
-        kv.mode = mode;
-    }
-    for (uint32_t j = 0; j < a.num_hashes; ++j) {
-        const uint64_t h = xxh64_view(kv, (uint64_t)j);
-        for (uint32_t i = 0; i < a.ndocs; ++i) {
-            const PlantDoc d = a.docs[i];
-            if (!d.col) continue;
-            if (mix64(a.salt ^ ((uint64_t)d.doc << 32) ^ (uint64_t)t) % 1000u >= d.keep_permille) continue;
-            uint8_t* byte = d.col + (h % d.sig) * (uint64_t)d.pitch;
-            const uintptr_t addr = reinterpret_cast<uintptr_t>(byte);
-            atomicOr(reinterpret_cast<uint32_t*>(addr & ~(uintptr_t)3), 1u << (8u * (uint32_t)(addr & 3u) + d.bit));
-        }
-    }
-}
-
-// rows [row0, row0 + nrows) of one sub-index of the procedural index, packed `pitch` bytes apart
-// (the file writer: cobs_gpu_write_synthetic)
-__global__ __launch_bounds__(256) void synth_rows_kernel(SynthRowsArgs a) {
-    const uint32_t wpr = a.pitch / 8u;
-    const uint64_t nwords = a.nrows * (uint64_t)wpr;
-    uint64_t* dst = reinterpret_cast<uint64_t*>(a.dst);
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nwords;
-         i += (uint64_t)gridDim.x * blockDim.x) {
-        const uint64_t r = i / wpr;
-        const uint32_t w = (uint32_t)(i - r * wpr);
-        const uint64_t x = synth_word(a.seed, a.page, a.row0 + r, w);
-        uint64_t v = 0;
-#pragma unroll
-        for (uint32_t b = 0; b < 8; ++b) {
-            const uint64_t gb = (uint64_t)w * 8u + b;          // row byte
-            uint32_t byte = (uint32_t)(x >> (8 * b)) & 0xFFu;
-            if (gb >= a.row_bytes || gb * 8 >= a.live_docs) byte = 0;
-            else if (gb * 8 + 8 > a.live_docs) byte &= (1u << (uint32_t)(a.live_docs - gb * 8)) - 1u;
-            v |= (uint64_t)byte << (8 * b);
-        }
-        dst[i] = v;
-    }
-}
-
-// staged raw rows -> pitched rows (16 bytes per thread), zero padding to the pitch
-__global__ __launch_bounds__(256) void repitch_kernel(RepitchArgs a) {
-    const uint32_t cpr = a.dst_pitch / 16u;
-    const uint64_t total = a.rows * cpr;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-         i += (uint64_t)gridDim.x * blockDim.x) {
-        const uint64_t row = i / cpr;
-        const uint32_t c = (uint32_t)(i - row * cpr);
-        const uint8_t* s = a.src + row * a.src_pitch + a.src_col0 + (uint64_t)c * 16u;
-        uint32_t w[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-        for (uint32_t b = 0; b < 16; ++b) {
-            if (c * 16u + b < a.copy_bytes) w[b >> 2] |= (uint32_t)s[b] << (8 * (b & 3u));
-        }
-        *reinterpret_cast<uint4*>(a.dst + row * a.dst_pitch + (uint64_t)c * 16u) =
-            make_uint4(w[0], w[1], w[2], w[3]);
-    }
-}
-
-// ---------------------------------------------------------------------------
-// launchers
-
-hipError_t launch_hash(const HashArgs& a, uint64_t total_threads, hipStream_t stream) {
-    if (total_threads == 0) return hipSuccess;
-    const uint64_t blocks = (total_threads + 255) / 256;
-    if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    if (a.term_size == 31) {
-        if (a.idx64) hipLaunchKernelGGL(hash_kernel_k31<uint64_t>, dim3((uint32_t)blocks), dim3(256), 0, stream, a, total_threads);
-        else hipLaunchKernelGGL(hash_kernel_k31<uint32_t>, dim3((uint32_t)blocks), dim3(256), 0, stream, a, total_threads);
-    } else {
-        if (a.idx64) hipLaunchKernelGGL(hash_kernel<uint64_t>, dim3((uint32_t)blocks), dim3(256), 0, stream, a, total_threads);
-        else hipLaunchKernelGGL(hash_kernel<uint32_t>, dim3((uint32_t)blocks), dim3(256), 0, stream, a, total_threads);
-    }
-    return hipGetLastError();
-}
-
-hipError_t launch_skip_thresholds(const SkipThresholdArgs& a, hipStream_t stream) {
-    if (a.nq == 0) return hipSuccess;
-    hipLaunchKernelGGL(skip_thresholds_kernel, dim3((a.nq + 255u) / 256u), dim3(256), 0, stream, a);
-    return hipGetLastError();
-}
+// launch side (host): one instantiation per (planes, waves, single hash, score type, multi-query, index width,
+// LDS-staged, tile top-k, findere).  This file instantiates the FZ = false ones, scan_findere.hip the FZ = true ones.
 
 template <int NP, int NW, bool H1, typename OutT, bool MQ = false, typename IdxT = uint32_t, bool LDSS = false, bool TK = false,
           bool FZ = false>
-static hipError_t launch_scan_inst(const ScanArgs& a, uint32_t ntiles, hipStream_t stream) {
-    (void)ntiles;
+static hipError_t launch_scan_inst(const ScanArgs& a, hipStream_t stream) {
     const uint32_t per_group = MQ ? 64u / a.tile_w : 1u;
     const uint64_t groups = (uint64_t)((a.chunk_end - a.chunk_begin + a.tile_w - 1) / a.tile_w) *
                             ((a.nq + per_group - 1u) / per_group);
@@ -1963,45 +1104,74 @@ static hipError_t launch_scan_inst(const ScanArgs& a, uint32_t ntiles, hipStream
     return hipGetLastError();
 }
 
-// multi-query variant: H = 1, u16 scores (short queries)
+// The launch dispatch over (waves per group x a flag): calls launch(std::integral_constant<int, NW>{},
+// std::bool_constant<FLAG>{}) for nw = 1, 2 or 4 (anything else counts as 4), as dispatch_idx_flag does for
+// (index width x flag).
+template <typename F>
+inline hipError_t dispatch_waves_flag(int nw, bool flag, F&& launch) {
+    using std::integral_constant;
+    if (nw == 1) return flag ? launch(integral_constant<int, 1>{}, std::true_type{}) : launch(integral_constant<int, 1>{}, std::false_type{});
+    if (nw == 2) return flag ? launch(integral_constant<int, 2>{}, std::true_type{}) : launch(integral_constant<int, 2>{}, std::false_type{});
+    return flag ? launch(integral_constant<int, 4>{}, std::true_type{}) : launch(integral_constant<int, 4>{}, std::false_type{});
+}
+
+// multi-query variant: H = 1 (short queries); the flag is "run_topk without score rows"
 template <int NP, typename OutT, bool FZ>
-static hipError_t launch_scan_mq(const ScanArgs& a, uint32_t ntiles, int nw, hipStream_t stream) {
-    if (a.cand) {           // run_topk without score rows
-        if (nw == 1) return launch_scan_inst<NP, 1, true, OutT, true, uint32_t, false, true, FZ>(a, ntiles, stream);
-        if (nw == 2) return launch_scan_inst<NP, 2, true, OutT, true, uint32_t, false, true, FZ>(a, ntiles, stream);
-        return launch_scan_inst<NP, 4, true, OutT, true, uint32_t, false, true, FZ>(a, ntiles, stream);
-    }
-    if (nw == 1) return launch_scan_inst<NP, 1, true, OutT, true, uint32_t, false, false, FZ>(a, ntiles, stream);
-    if (nw == 2) return launch_scan_inst<NP, 2, true, OutT, true, uint32_t, false, false, FZ>(a, ntiles, stream);
-    return launch_scan_inst<NP, 4, true, OutT, true, uint32_t, false, false, FZ>(a, ntiles, stream);
+static hipError_t launch_scan_mq(const ScanArgs& a, int nw, hipStream_t stream) {
+    return dispatch_waves_flag(nw, a.cand != nullptr, [&](auto w, auto tk) {
+        return launch_scan_inst<NP, decltype(w)::value, true, OutT, true, uint32_t, false, decltype(tk)::value, FZ>(a, stream);
+    });
 }
 
 template <int NP, typename OutT, bool FZ>
-static hipError_t launch_scan_np(const ScanArgs& a, uint32_t ntiles, bool h1, int nw, hipStream_t stream) {
+static hipError_t launch_scan_np(const ScanArgs& a, bool h1, int nw, hipStream_t stream) {
     if (a.cand) {           // run_topk without score rows: 32-bit row indices (scan_has_tile_topk)
         if (a.idx64) return hipErrorInvalidValue;
-        if (nw == 1) return h1 ? launch_scan_inst<NP, 1, true, OutT, false, uint32_t, false, true, FZ>(a, ntiles, stream)
-                               : launch_scan_inst<NP, 1, false, OutT, false, uint32_t, false, true, FZ>(a, ntiles, stream);
-        if (nw == 2) return h1 ? launch_scan_inst<NP, 2, true, OutT, false, uint32_t, false, true, FZ>(a, ntiles, stream)
-                               : launch_scan_inst<NP, 2, false, OutT, false, uint32_t, false, true, FZ>(a, ntiles, stream);
-        return h1 ? launch_scan_inst<NP, 4, true, OutT, false, uint32_t, false, true, FZ>(a, ntiles, stream)
-                  : launch_scan_inst<NP, 4, false, OutT, false, uint32_t, false, true, FZ>(a, ntiles, stream);
+        return dispatch_waves_flag(nw, h1, [&](auto w, auto h) {
+            return launch_scan_inst<NP, decltype(w)::value, decltype(h)::value, OutT, false, uint32_t, false, true, FZ>(a, stream);
+        });
     }
     if (a.idx64) {
         // sub-indexes with >= 2^32 rows: 64-bit row indices; two waves per group cover every
         // query length well enough for this rare geometry (keeps the instantiation count down)
-        return h1 ? launch_scan_inst<NP, 2, true, OutT, false, uint64_t, false, false, FZ>(a, ntiles, stream)
-                  : launch_scan_inst<NP, 2, false, OutT, false, uint64_t, false, false, FZ>(a, ntiles, stream);
+        return h1 ? launch_scan_inst<NP, 2, true, OutT, false, uint64_t, false, false, FZ>(a, stream)
+                  : launch_scan_inst<NP, 2, false, OutT, false, uint64_t, false, false, FZ>(a, stream);
     }
-    if (nw == 1)
-        return h1 ? launch_scan_inst<NP, 1, true, OutT, false, uint32_t, false, false, FZ>(a, ntiles, stream)
-                  : launch_scan_inst<NP, 1, false, OutT, false, uint32_t, false, false, FZ>(a, ntiles, stream);
-    if (nw == 2)
-        return h1 ? launch_scan_inst<NP, 2, true, OutT, false, uint32_t, false, false, FZ>(a, ntiles, stream)
-                  : launch_scan_inst<NP, 2, false, OutT, false, uint32_t, false, false, FZ>(a, ntiles, stream);
-    return h1 ? launch_scan_inst<NP, 4, true, OutT, false, uint32_t, false, false, FZ>(a, ntiles, stream)
-              : launch_scan_inst<NP, 4, false, OutT, false, uint32_t, false, false, FZ>(a, ntiles, stream);
+    return dispatch_waves_flag(nw, h1, [&](auto w, auto h) {
+        return launch_scan_inst<NP, decltype(w)::value, decltype(h)::value, OutT, false, uint32_t, false, false, FZ>(a, stream);
+    });
 }
+
+// every plain (FZ = false) or every findere (FZ = true) instantiation, by planes
+template <bool FZ>
+static hipError_t launch_scan_fz(const ScanArgs& a, int planes, int nw, bool multi_query, hipStream_t stream) {
+    const bool h1 = a.num_hashes == 1;
+    if (multi_query) {
+        if (a.idx64 || !scan_has_multi_query(planes, a.num_hashes, a.tile_w)) return hipErrorInvalidValue;
+        switch (planes) {
+        case 4: return launch_scan_mq<4, uint8_t, FZ>(a, nw, stream);
+        case 8: return launch_scan_mq<8, uint8_t, FZ>(a, nw, stream);
+        case 10: return launch_scan_mq<10, uint16_t, FZ>(a, nw, stream);
+        default: return launch_scan_mq<12, uint16_t, FZ>(a, nw, stream);
+        }
+    }
+    switch (planes) {
+    case 4: return launch_scan_np<4, uint8_t, FZ>(a, h1, nw, stream);
+    case 8: return launch_scan_np<8, uint8_t, FZ>(a, h1, nw, stream);
+    case 10: return launch_scan_np<10, uint16_t, FZ>(a, h1, nw, stream);
+    case 12: return launch_scan_np<12, uint16_t, FZ>(a, h1, nw, stream);
+    case 16: return launch_scan_np<16, uint16_t, FZ>(a, h1, nw, stream);
+    case 20: return launch_scan_np<20, uint32_t, FZ>(a, h1, nw, stream);
+    case 24: return launch_scan_np<24, uint32_t, FZ>(a, h1, nw, stream);
+    case 32: return launch_scan_np<32, uint32_t, FZ>(a, h1, nw, stream);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+// the findere half (scan_findere.hip), called by launch_scan below
+hipError_t launch_scan_findere(const ScanArgs& a, int planes, int nw, bool multi_query, hipStream_t stream);
+
+#ifndef COBS_SCAN_FINDERE_UNIT      // what follows is defined once, in the translation unit of this file
 
 int scan_planes_for(uint64_t max_terms) {
     int need = 1;
@@ -2022,140 +1192,22 @@ bool scan_has_lds_staged(int planes, uint32_t num_hashes, int nw) {
     return num_hashes == 1 && planes == 10 && (nw == 2 || nw == 4);
 }
 
-template <bool FZ>
-static hipError_t launch_scan_fz(const ScanArgs& a, uint32_t ntiles, int planes, int nw, bool multi_query, hipStream_t stream) {
-    const bool h1 = a.num_hashes == 1;
-    if (multi_query) {
-        if (a.idx64 || !scan_has_multi_query(planes, a.num_hashes, a.tile_w)) return hipErrorInvalidValue;
-        switch (planes) {
-        case 4: return launch_scan_mq<4, uint8_t, FZ>(a, ntiles, nw, stream);
-        case 8: return launch_scan_mq<8, uint8_t, FZ>(a, ntiles, nw, stream);
-        case 10: return launch_scan_mq<10, uint16_t, FZ>(a, ntiles, nw, stream);
-        default: return launch_scan_mq<12, uint16_t, FZ>(a, ntiles, nw, stream);
-        }
-    }
-    switch (planes) {
-    case 4: return launch_scan_np<4, uint8_t, FZ>(a, ntiles, h1, nw, stream);
-    case 8: return launch_scan_np<8, uint8_t, FZ>(a, ntiles, h1, nw, stream);
-    case 10: return launch_scan_np<10, uint16_t, FZ>(a, ntiles, h1, nw, stream);
-    case 12: return launch_scan_np<12, uint16_t, FZ>(a, ntiles, h1, nw, stream);
-    case 16: return launch_scan_np<16, uint16_t, FZ>(a, ntiles, h1, nw, stream);
-    case 20: return launch_scan_np<20, uint32_t, FZ>(a, ntiles, h1, nw, stream);
-    case 24: return launch_scan_np<24, uint32_t, FZ>(a, ntiles, h1, nw, stream);
-    case 32: return launch_scan_np<32, uint32_t, FZ>(a, ntiles, h1, nw, stream);
-    default: return hipErrorInvalidValue;
-    }
-}
 
 hipError_t launch_scan(const ScanArgs& a, uint32_t ntiles, int planes, int nw, bool multi_query,
                        hipStream_t stream) {
+    (void)ntiles;
     if (a.cand && (a.lds_staged || a.topk_k == 0 || !scan_has_tile_topk(a.num_hashes, a.idx64 != 0))) return hipErrorInvalidValue;
     if (a.findere > 7u || (a.findere && a.lds_staged)) return hipErrorInvalidValue;
     if (a.lds_staged) {     // measured variant (A/B): rows through LDS
         if (multi_query || a.idx64 || !scan_has_lds_staged(planes, a.num_hashes, nw)) return hipErrorInvalidValue;
-        return nw == 2 ? launch_scan_inst<10, 2, true, uint16_t, false, uint32_t, true>(a, ntiles, stream)
-                       : launch_scan_inst<10, 4, true, uint16_t, false, uint32_t, true>(a, ntiles, stream);
+        return nw == 2 ? launch_scan_inst<10, 2, true, uint16_t, false, uint32_t, true>(a, stream)
+                       : launch_scan_inst<10, 4, true, uint16_t, false, uint32_t, true>(a, stream);
     }
     // findere: its own instantiations, so that z = 0 launches exactly the plain kernels
-    return a.findere ? launch_scan_fz<true>(a, ntiles, planes, nw, multi_query, stream)
-                     : launch_scan_fz<false>(a, ntiles, planes, nw, multi_query, stream);
+    return a.findere ? launch_scan_findere(a, planes, nw, multi_query, stream)
+                     : launch_scan_fz<false>(a, planes, nw, multi_query, stream);
 }
 
-hipError_t launch_topk(const TopkArgs& a, hipStream_t stream) {
-    if (a.nq == 0 || a.k == 0) return hipSuccess;
-    if (a.level_bits == 0 || a.level_bits > 12 || a.levels == 0 || a.levels * a.level_bits < a.score_bits ||
-        (a.levels - 1) * a.level_bits >= a.score_bits)
-        return hipErrorInvalidValue;
-    const uint32_t nb = 1u << a.level_bits;
-    size_t lds = (size_t)(4 * nb + 256 + 16) * sizeof(uint32_t);
-    // the sort reuses the histogram area: 8 bytes per survivor
-    uint32_t m = 2;
-    while (m < a.sort_limit) m <<= 1;
-    if (a.sort_limit) lds = std::max(lds, (size_t)m * 8);
-    auto kern = a.from_pool ? topk_kernel<uint32_t, true>
-              : a.score_bytes == 1 ? topk_kernel<uint8_t> : a.score_bytes == 2 ? topk_kernel<uint16_t> : topk_kernel<uint32_t>;
-    if (a.score_bytes != 1 && a.score_bytes != 2 && a.score_bytes != 4) return hipErrorInvalidValue;
-    if (a.from_pool && ((a.counts_stride & 7u) != 0u || a.counts_stride < a.nslots)) return hipErrorInvalidValue;   // 64-byte rows
-    if (lds > 64 * 1024 + 2048) return hipErrorInvalidValue;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(kern, dim3(a.nq), dim3(256), lds, stream, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_select_rows(const SelectRowsArgs& a, hipStream_t stream) {
-    if (a.nq == 0 || a.nslots == 0) return hipSuccess;
-    if ((a.stride % 8u) != 0 || (a.elem_bytes != 1 && a.elem_bytes != 2 && a.elem_bytes != 4)) return hipErrorInvalidValue;
-    const uint64_t items = (uint64_t)a.nq * ((a.nslots + 7u) / 8u);
-    const uint64_t blocks = (items + 255u) / 256u;
-    if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    auto kern = a.elem_bytes == 1 ? select_rows_kernel<uint8_t> : a.elem_bytes == 2 ? select_rows_kernel<uint16_t> : select_rows_kernel<uint32_t>;
-    hipLaunchKernelGGL(kern, dim3((uint32_t)blocks), dim3(256), 0, stream, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_build(const BuildArgs& a, uint64_t total_bytes, hipStream_t stream) {
-    if (total_bytes == 0) return hipSuccess;
-    const uint64_t blocks = (total_bytes + 255) / 256;
-    if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(build_kernel, dim3((uint32_t)blocks), dim3(256), 0, stream, a, total_bytes);
-    return hipGetLastError();
-}
-
-hipError_t launch_pack_bytemap(const PackArgs& a, hipStream_t stream) {
-    if (a.ndocs == 0 || a.rows == 0) return hipSuccess;
-    const uint32_t nwords = ((a.col_base + a.ndocs - 1u) >> 5) - (a.col_base >> 5) + 1u;
-    const uint64_t threads = (a.rows + 3u) / 4u * nwords;
-    const uint64_t blocks = (threads + 255) / 256;
-    if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(pack_bytemap_kernel, dim3((uint32_t)blocks), dim3(256), 0, stream, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_random_build(const RandomBuildArgs& a, uint64_t ndocs, hipStream_t stream) {
-    const uint64_t total = ndocs * a.document_size;
-    if (total == 0) return hipSuccess;
-    const uint64_t blocks = (total + 255) / 256;
-    if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(random_build_kernel, dim3((uint32_t)blocks), dim3(256), 0, stream, a, total);
-    return hipGetLastError();
-}
-
-hipError_t launch_combine(const CombineArgs& a, hipStream_t stream) {
-    if (a.rows == 0 || a.dst_row_bytes == 0) return hipSuccess;
-    hipLaunchKernelGGL(combine_kernel, dim3(8192), dim3(256), 0, stream, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_synth(const SynthArgs& a, hipStream_t stream) {
-    if (a.npages == 0) return hipSuccess;
-    hipLaunchKernelGGL(synth_kernel, dim3(2048, a.npages), dim3(256), 0, stream, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_plant(const PlantArgs& a, hipStream_t stream) {
-    if (a.len < a.term_size || a.ndocs == 0) return hipSuccess;
-    const uint32_t terms = a.len - a.term_size + 1;
-    hipLaunchKernelGGL(plant_kernel, dim3((terms + 255) / 256), dim3(256), 0, stream, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_synth_rows(const SynthRowsArgs& a, hipStream_t stream) {
-    if (a.nrows == 0) return hipSuccess;
-    hipLaunchKernelGGL(synth_rows_kernel, dim3(4096), dim3(256), 0, stream, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_repitch(const RepitchArgs& a, hipStream_t stream) {
-    if (a.rows == 0) return hipSuccess;
-    const uint64_t total = a.rows * (a.dst_pitch / 16u);
-    uint64_t blocks = (total + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(repitch_kernel, dim3((uint32_t)blocks), dim3(256), 0, stream, a);
-    return hipGetLastError();
-}
+#endif  // COBS_SCAN_FINDERE_UNIT
 
 }  // namespace cobs_amd

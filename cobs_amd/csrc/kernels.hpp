@@ -48,7 +48,7 @@ hipError_t launch_gather_copy(const GatherArgs& a, uint32_t grid_limit, hipStrea
 // the rows a chunk holds; add a chunk's partial scores to the score rows.
 hipError_t launch_remap_rows(const RemapArgs& a, uint64_t entries, bool idx64, hipStream_t stream);
 hipError_t launch_add_scores(const AddScoresArgs& a, hipStream_t stream);
-// ... and the threshold filter over the scores a sub-index's row ranges added up (kernels.hip: select_rows_kernel)
+// ... and the threshold filter over the scores a sub-index's row ranges added up (topk_kernels.hip: select_rows_kernel)
 hipError_t launch_select_rows(const SelectRowsArgs& a, hipStream_t stream);
 // a row-range unit's in-range terms per query: a compact second table + its block offsets (count, scan, write)
 hipError_t launch_compact_terms(const CompactArgs& a, hipStream_t stream);

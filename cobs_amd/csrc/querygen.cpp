@@ -33,7 +33,7 @@ struct cobs_gpu_query_set {
 
 namespace {
 
-// draw i of seed S: the splitmix64 finaliser of S + i * 0x9E3779B97F4A7C15 (kernels.hip's mix64)
+// draw i of seed S: the splitmix64 finaliser of S + i * 0x9E3779B97F4A7C15 (build_kernels.hip's mix64)
 struct Draws {
     uint64_t seed, i = 0;
     explicit Draws(uint64_t s) : seed(s) {}

@@ -24,7 +24,7 @@
 namespace cobs_amd {
 namespace {
 
-// the splitmix64 finaliser (kernels.hip's mix64, kept local so that file stays as it is)
+// the splitmix64 finaliser (build_kernels.hip's mix64, kept local so that file stays as it is)
 __device__ __forceinline__ uint64_t qg_mix64(uint64_t z) {
     z += 0x9E3779B97F4A7C15ULL;
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;

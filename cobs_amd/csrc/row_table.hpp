@@ -1,4 +1,4 @@
-// cobs_amd/csrc/row_table.hpp -- THE definition of K1's row-index table, shared by its writer (hash_kernel, kernels.hip)
+// cobs_amd/csrc/row_table.hpp -- THE definition of K1's row-index table, shared by its writer (hash_kernel, hash_kernels.hip)
 // and every kernel that reads it (K2, the fetch kernels, presence, prevalence, weighted scan).
 //
 // Layout of one file's table:  [query q][held sub-index p][block b][hash j][8]

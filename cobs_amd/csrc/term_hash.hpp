@@ -1,6 +1,6 @@
 // cobs_amd/csrc/term_hash.hpp -- the __device__ code that turns a term into its signature rows,
-// shared by the kernels that hash terms: kernels.hip (hash_kernel, build_kernel, random_build_kernel,
-// plant_kernel) and abundance_kernels.hip (the min_count builder).  One definition of the
+// shared by the kernels that hash terms: hash_kernels.hip (hash_kernel), build_kernels.hip (build_kernel,
+// random_build_kernel, plant_kernel) and abundance_kernels.hip (the min_count builder).  One definition of the
 // canonicalisation (canonicalize_kmer, reference util/query.cpp:143-199), of XXH64 (public xxHash
 // specification) and of where a term's bit goes, so that every path sets the bits a query looks up.
 #pragma once

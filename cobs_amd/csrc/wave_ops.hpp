@@ -1,5 +1,5 @@
 // cobs_amd/csrc/wave_ops.hpp -- small device helpers more than one kernel file uses (gfx950, wave64): DPP cross-lane
-// moves, the lane-group sum built from them, the carry-save adder, a bit mask, and the launch dispatch over
+// moves, the lane-group sum and the wave scan built from them, the hit pool's append, the carry-save adder, a bit mask, and the launch dispatch over
 // (index width x single hash).  Include from .hip files only.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -33,6 +33,30 @@ __device__ __forceinline__ uint32_t group_sum_last(uint32_t c, uint32_t W) {
     if (W >= 32u) c += dpp_mov<kDppBcast15, 0xA, 0xF, false>(c);      // rows 1 and 3 += the total of the row before
     if (W >= 64u) c += dpp_mov<kDppBcast31, 0xC, 0xF, false>(c);      // rows 2 and 3 += the total of the first half
     return c;
+}
+
+// inclusive prefix sum over the 64 lanes of a wave: four row steps, then lane 15 / lane 31 broadcasts (GFX9 DPP)
+__device__ __forceinline__ uint32_t wave_incl_scan_dpp(uint32_t v) {
+    v += dpp_mov<kDppRowShr + 1>(v);
+    v += dpp_mov<kDppRowShr + 2>(v);
+    v += dpp_mov<kDppRowShr + 4>(v);
+    v += dpp_mov<kDppRowShr + 8>(v);
+    v += dpp_mov<kDppBcast15, 0xA, 0xF, false>(v);      // rows 1 and 3 += the total of the row before
+    v += dpp_mov<kDppBcast31, 0xC, 0xF, false>(v);      // rows 2 and 3 += the total of the first half
+    return v;
+}
+
+// Append to a pool with a 64-bit fill counter, one atomic per wave: lane `lane` brings n records (0: none) and gets
+// the position of its first one; its records go to consecutive positions from there.  The caller writes them and
+// checks every position against the pool's capacity (the counter may run past it: that is how overflow shows).  Called
+// by all 64 lanes of a wave, with converged control flow.
+__device__ __forceinline__ unsigned long long pool_append(uint32_t n, unsigned long long* counter, uint32_t lane) {
+    const uint32_t incl = wave_incl_scan_dpp(n);
+    const uint32_t total = __shfl(incl, 63);
+    unsigned long long base = 0ull;
+    if (lane == 63u) base = atomicAdd(counter, (unsigned long long)total);
+    base = __shfl(base, 63);
+    return base + incl - n;
 }
 
 // carry-save adder: (h, l) = a + b + c per bit position.  gfx950 has a three-input boolean op (v_bitop3_b32, 8-bit

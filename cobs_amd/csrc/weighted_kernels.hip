@@ -29,7 +29,7 @@
 #include <algorithm>
 
 #include "weighted_kernels.hpp"
-#include "wave_ops.hpp"      // csa, low_bits, dispatch_idx_flag
+#include "wave_ops.hpp"      // csa, low_bits, pool_append, dispatch_idx_flag
 
 namespace cobs_amd {
 
@@ -300,17 +300,7 @@ __global__ __launch_bounds__(256) void weighted_scan_kernel(WeightedScanArgs a) 
         cnt += (uint32_t)__popc(x);
     }
     if (!__any(cnt != 0u)) return;                          // (uniform)
-    uint32_t incl = cnt;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t t = (uint32_t)__shfl_up((int)incl, off);
-        if (lane >= (uint32_t)off) incl += t;
-    }
-    const uint32_t total = (uint32_t)__shfl((int)incl, 63);
-    unsigned long long base = 0ull;
-    if (lane == 63u) base = atomicAdd(a.fill, (unsigned long long)total);
-    const uint32_t blo = (uint32_t)__shfl((int)(uint32_t)base, 63), bhi = (uint32_t)__shfl((int)(uint32_t)(base >> 32), 63);
-    uint64_t pos = ((uint64_t)bhi << 32 | blo) + incl - cnt;
+    uint64_t pos = pool_append(cnt, a.fill, lane);
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
         uint32_t x = ge[c];

@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
-"""scripts/isa_resources.py [OUT] -- compile kernels.hip for gfx950 with --save-temps and list
+"""scripts/isa_resources.py [OUT [ASM_DIR]] -- compile the kernel files for gfx950 with --save-temps and list
 what the code object's metadata says every kernel uses (VGPRs, AGPRs, SGPRs, static LDS, scratch,
 spills) plus the occupancy that follows (512 VGPRs per SIMD lane on CDNA4, granule 8, at most 8
 waves per SIMD).  Runs without a GPU.  The summary is written to OUT (default
 profiles/isa_resources.txt) so that statements about registers / occupancy in DESIGN.md can be
 checked against the compiler's own numbers rather than against profiler dispatch fields
 (rocprofv3's VGPR_Count column reports the arch-VGPR allocation only and LDS_Block_Size does
-not include dynamic LDS)."""
+not include dynamic LDS).  With ASM_DIR the assembly is kept there, a directory per file, for
+scripts/isa_instr_diff.py."""
 import os
 import re
 import subprocess
@@ -14,13 +15,16 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KERNEL_FILES = ("kernels", "group_kernels", "fill_kernels", "prevalence_kernels", "weighted_kernels", "presence_kernels",
-                "fetch_kernels")
+KERNEL_FILES = ("hash_kernels", "kernels", "scan_findere", "topk_kernels", "build_kernels", "group_kernels", "fill_kernels",
+                "prevalence_kernels", "weighted_kernels", "presence_kernels", "fetch_kernels")
 
 
 def main():
     out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "isa_resources.txt")
-    # the scan kernels, the grouped-search kernels (group_kernels.hip: accumulate, select, zero) and the filter-fill
+    keep = sys.argv[2] if len(sys.argv) > 2 else None
+    # K1 (hash_kernels.hip), the scan kernels (kernels.hip: the kernel and its plain instantiations,
+    # scan_findere.hip the findere ones), K3 (topk_kernels.hip), construction (build_kernels.hip), the grouped-search
+    # kernels (group_kernels.hip: accumulate, select, zero) and the filter-fill
     # kernels (fill_kernels.hip: count, its load-only probe, zero), the prevalence kernels (prevalence_kernels.hip), the
     # kernels of the weighted search (weighted_kernels.hip: weights, weighted scan), and the other readers of K1's
     # row-index table (row_table.hpp): the presence kernel and the out-of-core fetch kernels
@@ -28,6 +32,9 @@ def main():
     for name in KERNEL_FILES:
         src = os.path.join(ROOT, "cobs_amd", "csrc", name + ".hip")
         with tempfile.TemporaryDirectory() as tmp:
+            if keep:
+                tmp = os.path.join(os.path.abspath(keep), name)
+                os.makedirs(tmp, exist_ok=True)
             subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
                                    "-I" + os.path.dirname(src), "--save-temps", "-c", src, "-o", "k.o"], cwd=tmp,
                                   stderr=subprocess.DEVNULL)
