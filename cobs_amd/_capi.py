@@ -15,6 +15,7 @@ OK = 0
 ERR_OPEN, ERR_FORMAT, ERR_QUERY_TOO_SHORT, ERR_INVALID_BASE, ERR_QUERY_TOO_LONG = 1, 2, 3, 4, 5
 ERR_HIP, ERR_ARG, ERR_UNSUPPORTED, ERR_CAPACITY, ERR_NO_DEVICE, ERR_RCCL = 6, 7, 8, 9, 10, 11
 XCHG_ALLGATHER, XCHG_ALLTOALL, XCHG_REDUCE = 0, 1, 2
+NO_SET, SETS_BY_ANY, SETS_BY_ALL = 0xFFFFFFFF, 0, 1
 UNIQUE_ID_BYTES = 128
 
 STATUS_NAMES = {
@@ -48,6 +49,10 @@ class Hit(C.Structure):
 
 class GroupHit(C.Structure):
     _fields_ = [("file_no", C.c_uint32), ("doc", C.c_uint32), ("score", C.c_uint32), ("votes", C.c_uint32)]
+
+
+class SetHit(C.Structure):
+    _fields_ = [("file_no", C.c_uint32), ("set", C.c_uint32), ("any", C.c_uint32), ("all", C.c_uint32)]
 
 
 class BuildParams(C.Structure):
@@ -169,6 +174,11 @@ SYMBOLS = {
     "cobs_gpu_search_weighted": (_int, [_vp, C.POINTER(_cp), C.POINTER(_sz), _sz, _dbl, _sz, C.POINTER(Hit), _sz,
                                         C.POINTER(_sz), _pu64, C.POINTER(_sz)]),
     "cobs_gpu_weighted_ms": (_int, [_vp, C.POINTER(C.c_double * 5)]),
+    "cobs_gpu_set_doc_sets": (_int, [_vp, _sz, C.POINTER(_u32), _sz, _u32]),
+    "cobs_gpu_get_doc_sets": (_int, [_vp, _sz, C.POINTER(_u32), C.POINTER(_u32), _sz]),
+    "cobs_gpu_search_sets": (_int, [_vp, C.POINTER(_cp), C.POINTER(_sz), _sz, _dbl, _u32, _sz, C.POINTER(SetHit), _sz,
+                                    C.POINTER(_sz), C.POINTER(_sz)]),
+    "cobs_gpu_sets_ms": (_int, [_vp, C.POINTER(C.c_double * 5)]),
     "cobs_gpu_search_groups": (_int, [_vp, C.POINTER(_cp), C.POINTER(_sz), _sz, C.POINTER(_sz), _sz, _dbl, _dbl, _sz,
                                       C.POINTER(GroupHit), _sz, C.POINTER(_sz), _pu64, C.POINTER(_sz)]),
     "cobs_gpu_groups_ms": (_int, [_vp, C.POINTER(C.c_double * 3)]),

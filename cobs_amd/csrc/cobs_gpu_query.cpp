@@ -21,6 +21,8 @@
 #include <memory>
 #include <random>
 #include <string>
+#include <unordered_map>
+#include <utility>
 #include <vector>
 
 #include "../../include/cobs_gpu_batch.h"          // cobs_gpu_write_synthetic (the generator sub-tool)
@@ -30,7 +32,7 @@
 static void usage() {
     std::fprintf(stderr,
                  "usage: cobs_gpu_query -i INDEX [-i INDEX ...] [-t THRESHOLD] [-l LIMIT] "
-                 "[-d DEVICE[,DEVICE...]] [--hbm-budget GIB] [--findere Z] [--invalid-bases MODE] [--positions] [--prevalence] [--weighted] [--fpr-adjust] (QUERY | -f QUERY_FILE)\n"
+                 "[-d DEVICE[,DEVICE...]] [--hbm-budget GIB] [--findere Z] [--invalid-bases MODE] [--positions] [--prevalence] [--weighted] [--fpr-adjust] [--sets FILE.tsv [--sets-by any|all]] (QUERY | -f QUERY_FILE)\n"
                  "       cobs_gpu_query doc-stats INDEX [--fill-above X]\n"
                  "         one line per document: file, name, sub-index, S_p, bits set in its filter, fill = bits / S_p, fpr = fill^H\n"
                  "       --fpr-adjust: every result line gets expected_fp (the positions the document's fill alone is expected to\n"
@@ -52,6 +54,12 @@ static void usage() {
                  "        holds and is a hit when that reaches -t of the query's total weight; same output as a plain query with\n"
                  "        the weighted score in place of the count (honours -l, --findere and --invalid-bases).  Not with several\n"
                  "        devices or --hbm-budget.\n"
+                 "       --sets FILE.tsv: score every query against SETS of documents; the file holds lines\n"
+                 "        document name<TAB>set name (a document it does not name is in no set; a name the index does not hold\n"
+                 "        is an error).  Per query its *comment line (with the number of sets), then set_name<TAB>any<TAB>all for\n"
+                 "        the sets that reach -t: any = the positions at least one member holds, all = the positions every\n"
+                 "        member holds; ordered by --sets-by any|all (default any), cut by -l (honours --findere and\n"
+                 "        --invalid-bases).  Not with several devices or --hbm-budget.\n"
                  "       --findere Z (0..7): a k-mer position scores only when Z + 1 consecutive k-mers are all present\n"
                  "        (findere, beyond `cobs query`: far fewer false-positive k-mers; a query needs k + Z characters)\n"
                  "       --invalid-bases error|miss|skip: a character outside ACGT fails the call (error, the default, as `cobs query`\n"
@@ -231,6 +239,74 @@ static void print_prevalence(cobs_gpu::ClassicSearch& s, const std::vector<std::
     }
 }
 
+// --sets FILE.tsv: lines `document name<TAB>set name`, read before the index is opened; false (with a message) for a file
+// that cannot be read or a line that is not of that form, or a document named twice with different sets
+static bool read_sets_tsv(const std::string& path, std::vector<std::pair<std::string, std::string>>& rows) {
+    std::ifstream in(path);
+    if (!in.good()) { std::fprintf(stderr, "--sets: could not open %s\n", path.c_str()); return false; }
+    std::unordered_map<std::string, std::string> seen;
+    std::string line;
+    for (size_t no = 1; std::getline(in, line); ++no) {
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        if (line.empty()) continue;
+        const size_t tab = line.find('\t');
+        if (tab == std::string::npos || tab == 0 || tab + 1 == line.size() || line.find('\t', tab + 1) != std::string::npos) {
+            std::fprintf(stderr, "--sets: line %zu of %s: expected document name<TAB>set name\n", no, path.c_str());
+            return false;
+        }
+        const std::string doc = line.substr(0, tab), set = line.substr(tab + 1);
+        const auto it = seen.find(doc);
+        if (it != seen.end() && it->second != set) {
+            std::fprintf(stderr, "--sets: line %zu of %s: document %s is already in set %s\n", no, path.c_str(), doc.c_str(), it->second.c_str());
+            return false;
+        }
+        if (it == seen.end()) {
+            seen.emplace(doc, set);
+            rows.emplace_back(doc, set);
+        }
+    }
+    return true;
+}
+
+// ... and its rows as labels of every index file: the set names numbered in sorted order (-> names), a document name the
+// index does not hold is an error that names it
+static void label_doc_sets(cobs_gpu::ClassicSearch& s, const std::vector<std::pair<std::string, std::string>>& rows,
+                           std::vector<std::string>& names) {
+    names.clear();
+    for (const auto& r : rows) names.push_back(r.second);
+    std::sort(names.begin(), names.end());
+    names.erase(std::unique(names.begin(), names.end()), names.end());
+    std::unordered_map<std::string, std::string> set_of(rows.begin(), rows.end());
+    std::unordered_map<std::string, bool> found;
+    const size_t nf = cobs_gpu_num_files(s.handle());
+    for (size_t f = 0; f < nf; ++f) {
+        cobs_gpu_index_info info;
+        if (cobs_gpu_info(s.handle(), f, &info) != COBS_GPU_OK) throw cobs_gpu::Error(COBS_GPU_ERR_ARG, cobs_gpu_last_error());
+        std::vector<uint32_t> labels(info.num_docs, COBS_GPU_NO_SET);
+        bool any = false;
+        for (uint64_t d = 0; d < info.num_docs; ++d) {
+            const auto it = set_of.find(cobs_gpu_doc_name(s.handle(), f, d));
+            if (it == set_of.end()) continue;
+            labels[d] = (uint32_t)(std::lower_bound(names.begin(), names.end(), it->second) - names.begin());
+            found[it->first] = true;
+            any = true;
+        }
+        if (any) s.set_doc_sets(labels, (uint32_t)names.size(), f);
+    }
+    for (const auto& r : rows)
+        if (!found.count(r.first)) throw cobs_gpu::Error(COBS_GPU_ERR_ARG, "--sets: the index holds no document named " + r.first);
+}
+
+static void print_sets(cobs_gpu::ClassicSearch& s, const std::vector<std::string>& queries, const std::vector<std::string>* comments,
+                       const std::vector<std::string>& names, double threshold, uint32_t rank_by, size_t num_results) {
+    std::vector<std::vector<cobs_gpu::ClassicSearch::SetResult>> results;
+    s.search_sets(queries, results, threshold, rank_by, num_results);
+    for (size_t q = 0; q < queries.size(); ++q) {
+        if (comments) std::cout << (*comments)[q] << '\t' << results[q].size() << '\n';
+        for (const auto& r : results[q]) std::cout << names[r.set] << '\t' << r.any << '\t' << r.all << '\n';
+    }
+}
+
 // --fpr-adjust: "\texpected_fp\tadjusted" of every result of one query.  Under --invalid-bases skip the positions are the
 // query's valid ones per file, read from a device batch of that one query (cobs_gpu_batch_scored_positions).
 static std::vector<cobs_gpu::ClassicSearch::Adjusted> adjusted_of(cobs_gpu::ClassicSearch& s, const std::string& query,
@@ -329,6 +405,7 @@ int main(int argc, char** argv) {
     bool prevalence = false;                 // --prevalence
     bool weighted = false;                   // --weighted
     bool fpr_adjust = false;                 // --fpr-adjust
+    std::string sets_file, sets_by;          // --sets FILE.tsv, --sets-by any|all
     std::string group;                       // --group N|all
     double read_threshold = 0.0;             // --read-threshold X
     unsigned num_kmers = 1000, num_queries = 10000, num_warmup = 100;
@@ -389,6 +466,8 @@ int main(int argc, char** argv) {
         else if (a == "--prevalence") prevalence = true;
         else if (a == "--weighted") weighted = true;
         else if (a == "--fpr-adjust") fpr_adjust = true;
+        else if (a == "--sets") sets_file = need("--sets");
+        else if (a == "--sets-by") sets_by = need("--sets-by");
         else if (a == "--group") group = need("--group");
         else if (a == "--read-threshold") read_threshold = std::atof(need("--read-threshold"));
         else if (a == "-h" || a == "--help") { usage(); return 0; }
@@ -413,6 +492,18 @@ int main(int argc, char** argv) {
                              "--fpr-adjust or --group\n");
         return 1;
     }
+    if (!sets_by.empty() && sets_by != "any" && sets_by != "all") { std::fprintf(stderr, "--sets-by: any or all\n"); return 1; }
+    if (!sets_by.empty() && sets_file.empty()) { std::fprintf(stderr, "--sets-by: needs --sets FILE.tsv\n"); return 1; }
+    if (!sets_file.empty() && (devices.size() > 1 || force_sharded || hbm_budget != 0 || positions || prevalence || weighted ||
+                               fpr_adjust || !group.empty())) {
+        std::fprintf(stderr, "--sets: not with several devices (-d A,B / --sharded: any and all are not additive over shards) or "
+                             "--hbm-budget (the rows have to be resident on one GPU), nor with --positions, --prevalence, "
+                             "--weighted, --fpr-adjust or --group\n");
+        return 1;
+    }
+    std::vector<std::pair<std::string, std::string>> set_rows;
+    if (!sets_file.empty() && !read_sets_tsv(sets_file, set_rows)) return 1;
+    const uint32_t sets_rank_by = sets_by == "all" ? COBS_GPU_SETS_BY_ALL : COBS_GPU_SETS_BY_ANY;
     size_t group_size = 0;                   // 0 with --group all
     if (fpr_adjust && (devices.size() > 1 || force_sharded || !group.empty())) {
         std::fprintf(stderr, "--fpr-adjust: not with several devices (-d A,B / --sharded: a document's filter lives on one rank) or --group\n");
@@ -503,6 +594,14 @@ int main(int argc, char** argv) {
     try {
         std::unique_ptr<cobs_gpu::BatchSearch> sp = open_index();
         cobs_gpu::BatchSearch& s = *sp;
+        std::vector<std::string> set_names;
+        if (!sets_file.empty()) label_doc_sets(dynamic_cast<cobs_gpu::ClassicSearch&>(s), set_rows, set_names);
+        if (!query_line.empty() && !sets_file.empty()) {
+            print_sets(dynamic_cast<cobs_gpu::ClassicSearch&>(s), {query_line}, nullptr, set_names, threshold, sets_rank_by, num_results);
+            std::cout.flush();
+            print_timer(s);
+            return 0;
+        }
         if (!query_line.empty() && prevalence) {
             print_prevalence(dynamic_cast<cobs_gpu::ClassicSearch&>(s), {query_line}, nullptr);
             std::cout.flush();
@@ -550,6 +649,12 @@ int main(int argc, char** argv) {
             }
         }
         if (!query.empty()) { queries.push_back(query); comments.push_back(comment); }
+        if (!sets_file.empty()) {
+            print_sets(dynamic_cast<cobs_gpu::ClassicSearch&>(s), queries, &comments, set_names, threshold, sets_rank_by, num_results);
+            std::cout.flush();
+            print_timer(s);
+            return 0;
+        }
         if (prevalence) {
             print_prevalence(dynamic_cast<cobs_gpu::ClassicSearch&>(s), queries, &comments);
             std::cout.flush();

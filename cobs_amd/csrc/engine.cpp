@@ -161,6 +161,7 @@ cobs_gpu_index::~cobs_gpu_index() {
     if (fill) destroy_fill_work(fill);
     if (prevalence) destroy_prevalence_work(prevalence);
     if (weighted) destroy_weighted_work(weighted);
+    if (sets) destroy_sets_work(sets);
     for (auto* b : scratch) delete b;
     if (xchg_stream) (void)hipStreamDestroy(xchg_stream);
 }

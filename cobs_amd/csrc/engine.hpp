@@ -301,6 +301,7 @@ struct GroupsWork;      // groups.cpp: scratch batches, accumulators and pool of
 struct FillWork;        // fill.cpp: cached per-document bit counts of cobs_gpu_doc_bits
 struct PrevalenceWork;  // prevalence.cpp: buffers of cobs_gpu_prevalence
 struct WeightedWork;    // weighted.cpp: cells, weights and hit pool of cobs_gpu_search_weighted
+struct SetsWork;        // sets.cpp: labels, segment records and bitmaps of cobs_gpu_search_sets
 
 }  // namespace cobs_amd
 
@@ -327,6 +328,7 @@ struct cobs_gpu_index {
     cobs_amd::FillWork* fill = nullptr;             // fill.cpp
     cobs_amd::PrevalenceWork* prevalence = nullptr; // prevalence.cpp
     cobs_amd::WeightedWork* weighted = nullptr;     // weighted.cpp
+    cobs_amd::SetsWork* sets = nullptr;             // sets.cpp
     ~cobs_gpu_index();
 };
 
@@ -566,6 +568,7 @@ void destroy_groups_work(GroupsWork* w);           // groups.cpp
 void destroy_fill_work(FillWork* w);               // fill.cpp
 void destroy_prevalence_work(PrevalenceWork* w);   // prevalence.cpp
 void destroy_weighted_work(WeightedWork* w);       // weighted.cpp
+void destroy_sets_work(SetsWork* w);               // sets.cpp
 void drop_fill_cache(cobs_gpu_index* ix, size_t file_no);   // ... the cached counts of one file (its bits changed)
 bool rank_on_device_applies(const cobs_gpu_batch* b, size_t nq);
 cobs_gpu_status rank_launch(cobs_gpu_batch* b, size_t q_first, size_t nq, size_t limit);

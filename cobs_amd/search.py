@@ -17,7 +17,7 @@ import sys
 import numpy as np
 
 from . import _capi
-from ._capi import CobsGpuError, GroupHit, Hit, IndexInfo, Options, Synth, check
+from ._capi import CobsGpuError, GroupHit, Hit, IndexInfo, Options, SetHit, Synth, check
 
 
 class SearchResult:
@@ -80,6 +80,58 @@ class WeightedResult(SearchResult):
 
     def __repr__(self):
         return "WeightedResult(doc_name=%r, score=%d, total_weight=%d)" % (self.doc_name, self.score, self.total_weight)
+
+
+class SetResult:
+    """one set of documents of a set result (Search.search_sets): any = the positions of the query at least one member of
+    the set holds, all = the positions every member holds; name = the set's name (its number as text when the labels were
+    given as numbers)"""
+    __slots__ = ("file_no", "set", "name", "any", "all")
+
+    def __init__(self, file_no=0, set=0, name="", any=0, all=0):
+        self.file_no = file_no
+        self.set = set
+        self.name = name
+        self.any = any
+        self.all = all
+
+    def __repr__(self):
+        return "SetResult(file_no=%d, set=%d, name=%r, any=%d, all=%d)" % (self.file_no, self.set, self.name, self.any, self.all)
+
+    def __eq__(self, other):
+        return (isinstance(other, SetResult) and (self.file_no, self.set, self.name, self.any, self.all) ==
+                (other.file_no, other.set, other.name, other.any, other.all))
+
+
+def doc_set_labels(labels, doc_names):
+    """the labels of one file as cobs_gpu_set_doc_sets takes them -> (uint32 [len(doc_names)], set names): `labels` is an
+    integer array with one entry per document, -1 (or 0xFFFFFFFF) for "in no set" -- the sets are then named by their
+    numbers --, or a {document name: set name} mapping -- the set names are numbered in sorted order, a document the mapping
+    does not name is in no set, a name the index does not hold is a ValueError that names it.  Host arithmetic only."""
+    n = len(doc_names)
+    if isinstance(labels, collections.abc.Mapping):
+        known = {name: d for d, name in enumerate(doc_names)}
+        for name in labels:
+            if name not in known:
+                raise ValueError("set_doc_sets: the index holds no document named %r" % (name,))
+        names = sorted({str(v) for v in labels.values()})
+        number = {s: i for i, s in enumerate(names)}
+        out = np.full(n, _capi.NO_SET, dtype=np.uint32)
+        for name, s in labels.items():
+            out[known[name]] = number[str(s)]
+        return out, names
+    arr = np.asarray(labels)
+    if arr.ndim != 1 or len(arr) != n:
+        raise ValueError("set_doc_sets: one label per document (%d), got shape %s" % (n, arr.shape))
+    if arr.dtype.kind not in "iu":
+        raise ValueError("set_doc_sets: integer labels, -1 for a document in no set")
+    wide = arr.astype(np.int64)
+    wide[wide == _capi.NO_SET] = -1
+    if (wide < -1).any() or (wide >= _capi.NO_SET).any():
+        raise ValueError("set_doc_sets: a label is a set number >= 0, or -1")
+    out = np.where(wide < 0, _capi.NO_SET, wide).astype(np.uint32)
+    n_sets = int(wide.max()) + 1 if n and wide.max() >= 0 else 0
+    return out, [str(i) for i in range(n_sets)]
 
 
 def fpr_adjust(score, positions, bits, sig, num_hashes, z=0):
@@ -813,6 +865,89 @@ class Search:
         t = (C.c_double * 5)()
         check(self._lib.cobs_gpu_weighted_ms(self._h, C.byref(t)))
         return {"hash_ms": t[0], "prevalence_ms": t[1], "weights_ms": t[2], "scan_ms": t[3], "passes": int(t[4])}
+
+    # -- document sets: score a query against labelled groups of documents ----------
+    SET_HIT_DTYPE = np.dtype([("file_no", "<u4"), ("set", "<u4"), ("any", "<u4"), ("all", "<u4")])
+    SETS_RANK_BY = ("any", "all")           # COBS_GPU_SETS_BY_ANY / _BY_ALL
+
+    def _sets_refuse_device_list(self):
+        if type(self)._search_batch_call is not Search._search_batch_call:
+            raise CobsGpuError(_capi.ERR_UNSUPPORTED, "sets: not on a device-list handle (any and all are not additive over shards)")
+
+    def set_doc_sets(self, labels, file_no=0):
+        """cobs_gpu_set_doc_sets: label the documents of file `file_no` with sets -- an integer array (-1: in no set) or a
+        {doc_name: set_name} mapping (doc_set_labels) -- and return the set names, set number i -> names[i].  None clears
+        the file's labels."""
+        self._sets_refuse_device_list()
+        names_of = self.__dict__.setdefault("_set_names", {})
+        if labels is None:
+            check(self._lib.cobs_gpu_set_doc_sets(self._h, int(file_no), None, 0, 0))
+            names_of.pop(int(file_no), None)
+            return []
+        arr, names = doc_set_labels(labels, self._names(int(file_no)))
+        arr = np.ascontiguousarray(arr, dtype=np.uint32)
+        check(self._lib.cobs_gpu_set_doc_sets(self._h, int(file_no), C.cast(arr.ctypes.data, C.POINTER(C.c_uint32)), len(arr),
+                                              len(names)))
+        names_of[int(file_no)] = names
+        return names
+
+    def doc_sets(self, file_no=0):
+        """cobs_gpu_get_doc_sets -> (set names, members uint32 [n_sets]): how many documents every set of the file holds;
+        ([], empty) for a file without labels"""
+        n = C.c_uint32(0)
+        check(self._lib.cobs_gpu_get_doc_sets(self._h, int(file_no), C.byref(n), None, 0))
+        members = np.zeros(n.value, dtype=np.uint32)
+        if n.value:
+            check(self._lib.cobs_gpu_get_doc_sets(self._h, int(file_no), C.byref(n), C.cast(members.ctypes.data, C.POINTER(C.c_uint32)),
+                                                  members.size))
+        names = self.__dict__.get("_set_names", {}).get(int(file_no))
+        if names is None or len(names) != n.value:
+            names = [str(i) for i in range(n.value)]
+        return list(names), members
+
+    def search_sets_arrays(self, queries, threshold=0.0, rank_by="any", num_results=0):
+        """cobs_gpu_search_sets -> (offsets uint64 [nq + 1], hits SET_HIT_DTYPE): the records of query q are
+        hits[offsets[q]:offsets[q + 1]] -- one per non-empty set of every labelled file whose key (any or all, by rank_by)
+        reaches max(1, ceil(threshold * P)) --, by key descending, then the other count descending, then (file_no, set)."""
+        self._sets_refuse_device_list()
+        if rank_by not in self.SETS_RANK_BY:
+            raise ValueError("rank_by: 'any' or 'all'")
+        qs = [q if type(q) is bytes else _as_bytes(q) for q in queries]
+        nq = len(qs)
+        arr = (C.c_char_p * max(nq, 1))(*qs)
+        lens = (C.c_size_t * max(nq, 1))(*[len(q) for q in qs])
+        offs = np.zeros(nq + 1, dtype=np.uint64)
+        bad = C.c_size_t(0)
+        per_query = sum(int(np.count_nonzero(self.doc_sets(f)[1])) for f in range(self.num_files))
+        cap = max(1, nq * (min(int(num_results), per_query) if num_results > 0 else per_query))
+        while True:
+            hits = np.zeros(cap, dtype=self.SET_HIT_DTYPE)
+            st = self._lib.cobs_gpu_search_sets(
+                self._h, arr, lens, nq, float(threshold), self.SETS_RANK_BY.index(rank_by), int(num_results),
+                C.cast(hits.ctypes.data, C.POINTER(SetHit)), cap, C.cast(offs.ctypes.data, C.POINTER(C.c_size_t)), C.byref(bad))
+            if st == _capi.ERR_CAPACITY and int(offs[nq]) > cap:
+                cap = int(offs[nq])
+                continue
+            check(st)
+            break
+        return offs, hits[:int(offs[nq])]
+
+    def search_sets(self, queries, threshold=0.0, rank_by="any", num_results=0):
+        """-> one list per query of SetResult(file_no, set, name, any, all) in result order; one str / bytes query -> its list"""
+        single = isinstance(queries, (str, bytes, bytearray))
+        qs = [queries] if single else list(queries)
+        offs, hits = self.search_sets_arrays(qs, threshold, rank_by, num_results)
+        names = {f: self.doc_sets(f)[0] for f in range(self.num_files)}
+        rows = hits.tolist()
+        out = [[SetResult(f, s, names[f][s], a, b) for (f, s, a, b) in rows[int(offs[q]):int(offs[q + 1])]] for q in range(len(qs))]
+        return out[0] if single else out
+
+    def sets_ms(self):
+        """stage times of the set searches since the previous call of this method (HIP events, summed over passes; the
+        ordering on the host clock)"""
+        t = (C.c_double * 5)()
+        check(self._lib.cobs_gpu_sets_ms(self._h, C.byref(t)))
+        return {"hash_ms": t[0], "presence_ms": t[1], "select_ms": t[2], "order_ms": t[3], "passes": int(t[4])}
 
     # -- grouped search: which documents a SET of queries comes from -----------------
     GROUP_HIT_DTYPE = np.dtype([("file_no", "<u4"), ("doc", "<u4"), ("score", "<u4"), ("votes", "<u4")])

@@ -226,6 +226,53 @@ cobs_gpu_status cobs_gpu_search_weighted(cobs_gpu_index* ix, const char* const* 
                                          cobs_gpu_hit* hits, size_t cap, size_t* hit_offsets /* nq + 1 */,
                                          uint64_t* total_weight /* optional, nq * n_files: W(q,f) */, size_t* bad_query);
 
+/* ---- document sets ------------------------------------------------------- */
+/* Score a query against labelled SETS of documents (the assemblies of a species, a lineage, an outbreak, the runs of a
+ * sample), beyond the reference.  Labels are per file: label[d] of the real documents d < D_f of file f is a set number in
+ * [0, n_sets) or COBS_GPU_NO_SET (the document is in no set).  A set without a member in a file does not exist for that
+ * file.  With T = len - term_size(f) + 1 terms and the handle's findere z a query has n = T - z positions in file f;
+ * position p is set in document d exactly as cobs_gpu_prevalence and cobs_gpu_hit_positions define it (terms p .. p + z all
+ * present, every hash bit set, the invalid-bases policy through K1's table).  For a non-empty set c of file f:
+ *   any(q, f, c) = the positions set in AT LEAST ONE member of c (the pan-genome score: robust against gaps in any one member),
+ *   all(q, f, c) = the positions set in EVERY member of c (the core score).
+ * Padding slots and unlabelled documents never take part, whatever bits the file holds there.  A one-member set has
+ * any == all == the score cobs_gpu_search_batch reports for that document; with every document of a file in one set, any =
+ * the positions with prevalence > 0 and all = the positions with prevalence == D_f; always all <= min and max <= any over
+ * the members' scores, and any <= n.
+ * cobs_gpu_set_doc_sets: n_docs must equal the file's real document count; labels == NULL clears the file's labels; labels
+ * replace earlier ones.  At most 2^28 sets per file.  The labels become segment records per 16-byte column chunk, built on
+ * the host and uploaded once.  cobs_gpu_get_doc_sets: *n_sets = the n_sets of the file's labels (0: none); members
+ * (optional, cap >= n_sets entries, else COBS_GPU_ERR_CAPACITY) receives the member count of every set.
+ * cobs_gpu_search_sets: a set is a hit when its key (any or all, by rank_by) is >= max(1, ceil(threshold * P)), computed in
+ * double; P is the denominator the search uses for that query and file -- n under ERROR and MISS, the V of
+ * cobs_gpu_batch_scored_positions under SKIP (the rule of a one-query group of cobs_gpu_search_groups); P = 0 returns
+ * nothing.  threshold <= 0 returns every non-empty set of every labelled file, key 0 included.  Per query the records are
+ * ordered by key descending, then the other count descending, then (file_no, set) ascending, and cut to num_results when it
+ * is > 0; the reference's "max_counts <= 1: index order" rule does NOT apply.  hits[hit_offsets[q] .. hit_offsets[q+1])
+ * belong to query q.  A file without labels contributes nothing.
+ * Everything the host can refuse is refused before any device work: COBS_GPU_ERR_ARG (NULL arguments, an n_docs mismatch, a
+ * label >= n_sets that is not COBS_GPU_NO_SET, rank_by > 1), COBS_GPU_ERR_QUERY_TOO_SHORT / _TOO_LONG (*bad_query = the
+ * offending query), COBS_GPU_ERR_UNSUPPORTED on a handle opened with an HBM budget or as one shard of several (any and all
+ * are not additive over shards: that takes an exchange of the bitmaps; the mirrors also refuse on the device list),
+ * COBS_GPU_ERR_HIP, with a message, when the two bitmaps of a single query do not fit the pass workspace (tuning key
+ * pass_bytes).  COBS_GPU_ERR_INVALID_BASE comes from the device (*bad_query).  COBS_GPU_ERR_CAPACITY when cap is too small --
+ * hit_offsets then holds the needed sizes (hit_offsets[nq] the total; hits may be NULL when cap is 0).
+ * On the device: K1, a presence kernel that ORs two bit matrices [query][set][ceil(n / 32)] together (the gather of the
+ * prevalence kernel reduced over labelled subsets of the columns), and a select kernel; passes are cut by pass_bytes and the
+ * results do not depend on the cut.  cobs_gpu_sets_ms (cobs_gpu_diag.h) reads the stage timers. */
+#define COBS_GPU_NO_SET 0xFFFFFFFFu
+#define COBS_GPU_SETS_BY_ANY 0u
+#define COBS_GPU_SETS_BY_ALL 1u
+typedef struct cobs_gpu_set_hit { uint32_t file_no, set, any, all; } cobs_gpu_set_hit;   /* 16 bytes */
+cobs_gpu_status cobs_gpu_set_doc_sets(cobs_gpu_index* ix, size_t file_no, const uint32_t* labels, size_t n_docs,
+                                      uint32_t n_sets);
+cobs_gpu_status cobs_gpu_get_doc_sets(const cobs_gpu_index* ix, size_t file_no, uint32_t* n_sets,
+                                      uint32_t* members /* optional, n_sets entries */, size_t cap);
+cobs_gpu_status cobs_gpu_search_sets(cobs_gpu_index* ix, const char* const* queries, const size_t* lens, size_t nq,
+                                     double threshold, uint32_t rank_by, size_t num_results,
+                                     cobs_gpu_set_hit* hits, size_t cap, size_t* hit_offsets /* nq + 1 */,
+                                     size_t* bad_query);
+
 /* score slots per query held by THIS shard (== cobs_gpu_total_counts when
  * unsharded); device count rows have this many elements */
 uint64_t cobs_gpu_local_counts(const cobs_gpu_index* ix);

@@ -88,6 +88,11 @@ cobs_gpu_status cobs_gpu_prevalence_ms(cobs_gpu_index* ix, double out[3]);
  * kernel, out[3] = the weighted scan (a scan repeated after a pool overflow included), out[4] = passes. */
 cobs_gpu_status cobs_gpu_weighted_ms(cobs_gpu_index* ix, double out[5]);   /* hash, prevalence, weights, scan, passes; reset on read */
 
+/* Durations (ms) of the stages of the cobs_gpu_search_sets calls on this handle since the previous call of this function,
+ * summed over their passes: out[0] = K1 (hashing), out[1] = the set presence kernel, out[2] = the select kernel (HIP
+ * events), out[3] = the host's ordering of the records, out[4] = passes. */
+cobs_gpu_status cobs_gpu_sets_ms(cobs_gpu_index* ix, double out[5]);   /* hash, presence, select, ordering, passes; reset on read */
+
 /* Durations (ms) of the LAST cobs_gpu_search_groups call on this handle: out[0] = the accumulate kernel (HIP events, summed
  * over the call's passes), out[1] = the select kernel (HIP events), out[2] = the host's ordering of the records. */
 cobs_gpu_status cobs_gpu_groups_ms(cobs_gpu_index* ix, double out[3]);

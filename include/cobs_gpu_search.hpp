@@ -378,6 +378,46 @@ public:
         }
     }
 
+    //! one set of documents of a set result: the positions at least one member holds, and the positions every member holds
+    struct SetResult {
+        uint32_t file_no, set, any, all;
+    };
+
+    //! label the documents of a file with sets (beyond the reference; cobs_gpu_set_doc_sets): labels[d] is a set number
+    //! below n_sets or COBS_GPU_NO_SET, one entry per document of the file; the labels replace earlier ones
+    void set_doc_sets(const std::vector<uint32_t>& labels, uint32_t n_sets, size_t file_no = 0) {
+        if (labels.empty()) throw Error(COBS_GPU_ERR_ARG, "set_doc_sets needs one label per document (clear_doc_sets takes labels away)");
+        check(cobs_gpu_set_doc_sets(ix_, file_no, labels.data(), labels.size(), n_sets));
+    }
+    //! ... and take them away again
+    void clear_doc_sets(size_t file_no = 0) { check(cobs_gpu_set_doc_sets(ix_, file_no, nullptr, 0, 0)); }
+
+    //! score every query against every non-empty set of every labelled file (cobs_gpu_search_sets): results[q] holds the
+    //! sets whose key -- any, or all with rank_by = COBS_GPU_SETS_BY_ALL -- reaches max(1, ceil(threshold * P)), by key
+    //! descending, then the other count descending, then (file, set)
+    void search_sets(const std::vector<std::string>& queries, std::vector<std::vector<SetResult>>& results,
+                     double threshold = 0.0, uint32_t rank_by = COBS_GPU_SETS_BY_ANY, size_t num_results = 0) {
+        std::vector<const char*> qp;
+        std::vector<size_t> ql;
+        for (const auto& q : queries) { qp.push_back(q.data()); ql.push_back(q.size()); }
+        const size_t nq = queries.size();
+        std::vector<size_t> offs(nq + 1, 0);
+        std::vector<cobs_gpu_set_hit> hits(16 * nq + 1024);
+        size_t bad = 0;
+        cobs_gpu_status st;
+        for (;;) {
+            st = cobs_gpu_search_sets(ix_, qp.data(), ql.data(), nq, threshold, rank_by, num_results, hits.data(), hits.size(),
+                                      offs.data(), &bad);
+            if (st != COBS_GPU_ERR_CAPACITY || offs[nq] <= hits.size()) break;
+            hits.resize(offs[nq]);          // (the call reported the needed size)
+        }
+        check(st);
+        results.assign(nq, {});
+        for (size_t q = 0; q < nq; ++q)
+            for (size_t i = offs[q]; i < offs[q + 1]; ++i)
+                results[q].push_back(SetResult{hits[i].file_no, hits[i].set, hits[i].any, hits[i].all});
+    }
+
     //! one document of a group's result: the sum of the scores of the group's queries and how many of them it was a hit of
     struct GroupResult {
         const char* doc_name;
