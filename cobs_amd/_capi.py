@@ -179,6 +179,10 @@ SYMBOLS = {
     "cobs_gpu_search_sets": (_int, [_vp, C.POINTER(_cp), C.POINTER(_sz), _sz, _dbl, _u32, _sz, C.POINTER(SetHit), _sz,
                                     C.POINTER(_sz), C.POINTER(_sz)]),
     "cobs_gpu_sets_ms": (_int, [_vp, C.POINTER(C.c_double * 5)]),
+    "cobs_gpu_covered_bases": (_u64, [_pu64, _sz, _u32]),
+    "cobs_gpu_search_coverage": (_int, [_vp, C.POINTER(_cp), C.POINTER(_sz), _sz, _dbl, _sz, C.POINTER(Hit), _sz,
+                                        C.POINTER(_sz), C.POINTER(_sz)]),
+    "cobs_gpu_coverage_ms": (_int, [_vp, C.POINTER(C.c_double * 3)]),
     "cobs_gpu_search_groups": (_int, [_vp, C.POINTER(_cp), C.POINTER(_sz), _sz, C.POINTER(_sz), _sz, _dbl, _dbl, _sz,
                                       C.POINTER(GroupHit), _sz, C.POINTER(_sz), _pu64, C.POINTER(_sz)]),
     "cobs_gpu_groups_ms": (_int, [_vp, C.POINTER(C.c_double * 3)]),

@@ -32,7 +32,7 @@
 static void usage() {
     std::fprintf(stderr,
                  "usage: cobs_gpu_query -i INDEX [-i INDEX ...] [-t THRESHOLD] [-l LIMIT] "
-                 "[-d DEVICE[,DEVICE...]] [--hbm-budget GIB] [--findere Z] [--invalid-bases MODE] [--positions] [--prevalence] [--weighted] [--fpr-adjust] [--sets FILE.tsv [--sets-by any|all]] (QUERY | -f QUERY_FILE)\n"
+                 "[-d DEVICE[,DEVICE...]] [--hbm-budget GIB] [--findere Z] [--invalid-bases MODE] [--positions] [--prevalence] [--weighted] [--coverage] [--fpr-adjust] [--sets FILE.tsv [--sets-by any|all]] (QUERY | -f QUERY_FILE)\n"
                  "       cobs_gpu_query doc-stats INDEX [--fill-above X]\n"
                  "         one line per document: file, name, sub-index, S_p, bits set in its filter, fill = bits / S_p, fpr = fill^H\n"
                  "       --fpr-adjust: every result line gets expected_fp (the positions the document's fill alone is expected to\n"
@@ -54,6 +54,11 @@ static void usage() {
                  "        holds and is a hit when that reaches -t of the query's total weight; same output as a plain query with\n"
                  "        the weighted score in place of the count (honours -l, --findere and --invalid-bases).  Not with several\n"
                  "        devices or --hbm-budget.\n"
+                 "       --coverage: coverage search -- a document scores the query BASES that lie inside a k-mer it holds (with\n"
+                 "        --findere Z: inside a window of Z + 1 present k-mers) and is a hit when that reaches -t of the query's\n"
+                 "        length: a read with one substitution keeps all but one of its bases; same output as a plain query\n"
+                 "        with the covered bases in place of the count (honours -l, --findere and --invalid-bases).  Not with\n"
+                 "        several devices or --hbm-budget.\n"
                  "       --sets FILE.tsv: score every query against SETS of documents; the file holds lines\n"
                  "        document name<TAB>set name (a document it does not name is in no set; a name the index does not hold\n"
                  "        is an error).  Per query its *comment line (with the number of sets), then set_name<TAB>any<TAB>all for\n"
@@ -404,6 +409,7 @@ int main(int argc, char** argv) {
     bool positions = false;                  // --positions
     bool prevalence = false;                 // --prevalence
     bool weighted = false;                   // --weighted
+    bool coverage = false;                   // --coverage
     bool fpr_adjust = false;                 // --fpr-adjust
     std::string sets_file, sets_by;          // --sets FILE.tsv, --sets-by any|all
     std::string group;                       // --group N|all
@@ -465,6 +471,7 @@ int main(int argc, char** argv) {
         else if (a == "--positions") positions = true;
         else if (a == "--prevalence") prevalence = true;
         else if (a == "--weighted") weighted = true;
+        else if (a == "--coverage") coverage = true;
         else if (a == "--fpr-adjust") fpr_adjust = true;
         else if (a == "--sets") sets_file = need("--sets");
         else if (a == "--sets-by") sets_by = need("--sets-by");
@@ -490,6 +497,12 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "--weighted: not with several devices (-d A,B / --sharded: the weights need every shard's counts) or "
                              "--hbm-budget (the rows have to be resident on one GPU), nor with --positions, --prevalence, "
                              "--fpr-adjust or --group\n");
+        return 1;
+    }
+    if (coverage && (devices.size() > 1 || force_sharded || hbm_budget != 0 || positions || prevalence || weighted || fpr_adjust ||
+                     !group.empty() || !sets_file.empty())) {
+        std::fprintf(stderr, "--coverage: not with several devices (-d A,B / --sharded) or --hbm-budget (the rows have to be "
+                             "resident on one GPU), nor with --positions, --prevalence, --weighted, --sets, --fpr-adjust or --group\n");
         return 1;
     }
     if (!sets_by.empty() && sets_by != "any" && sets_by != "all") { std::fprintf(stderr, "--sets-by: any or all\n"); return 1; }
@@ -608,6 +621,14 @@ int main(int argc, char** argv) {
             print_timer(s);
             return 0;
         }
+        if (!query_line.empty() && coverage) {
+            std::vector<std::vector<cobs_gpu::SearchResult>> results;
+            dynamic_cast<cobs_gpu::ClassicSearch&>(s).search_coverage({query_line}, results, threshold, num_results);
+            for (const auto& r : results[0]) std::cout << r.doc_name << '\t' << r.score << '\n';
+            std::cout.flush();
+            print_timer(s);
+            return 0;
+        }
         if (!query_line.empty() && weighted) {
             std::vector<std::vector<cobs_gpu::SearchResult>> results;
             dynamic_cast<cobs_gpu::ClassicSearch&>(s).search_weighted({query_line}, results, threshold, num_results);
@@ -657,6 +678,17 @@ int main(int argc, char** argv) {
         }
         if (prevalence) {
             print_prevalence(dynamic_cast<cobs_gpu::ClassicSearch&>(s), queries, &comments);
+            std::cout.flush();
+            print_timer(s);
+            return 0;
+        }
+        if (coverage) {
+            std::vector<std::vector<cobs_gpu::SearchResult>> results;
+            dynamic_cast<cobs_gpu::ClassicSearch&>(s).search_coverage(queries, results, threshold, num_results);
+            for (size_t q = 0; q < queries.size(); ++q) {
+                std::cout << comments[q] << '\t' << results[q].size() << '\n';
+                for (const auto& r : results[q]) std::cout << r.doc_name << '\t' << r.score << '\n';
+            }
             std::cout.flush();
             print_timer(s);
             return 0;

@@ -204,6 +204,17 @@ def unpack_positions(words, n):
     return np.unpackbits(w.view(np.uint8), bitorder="little")[:n].astype(bool)
 
 
+def covered_bases(words, n, span):
+    """cobs_gpu_covered_bases: the query bases covered by the set positions of one hit's words (Search.hit_positions; n
+    positions, a set position covers span = term size + findere bases) -- what Search.search_coverage scores the
+    document with.  Host arithmetic, no device; bits at or beyond n are ignored."""
+    w = np.ascontiguousarray(words, dtype="<u8")
+    n = int(n)
+    if n < 0 or len(w) * 64 < n:
+        raise ValueError("words holds fewer than n positions")
+    return int(_capi.load().cobs_gpu_covered_bases(C.cast(w.ctypes.data, C.POINTER(C.c_uint64)), n, int(span)))
+
+
 def _as_bytes(q):
     return q.encode("latin-1") if isinstance(q, str) else bytes(q)
 
@@ -865,6 +876,59 @@ class Search:
         t = (C.c_double * 5)()
         check(self._lib.cobs_gpu_weighted_ms(self._h, C.byref(t)))
         return {"hash_ms": t[0], "prevalence_ms": t[1], "weights_ms": t[2], "scan_ms": t[3], "passes": int(t[4])}
+
+    # -- coverage search: score documents by the query bases they cover ---------------
+    def search_coverage_arrays(self, queries, threshold=0.0, num_results=0):
+        """cobs_gpu_search_coverage -> (offsets uint64 [nq + 1], hits HIT_DTYPE): the records of query q are
+        hits[offsets[q]:offsets[q + 1]], by coverage descending, then (file_no, doc); `score` is the number of query bases
+        that lie inside a set position (span = term size + findere bases from the position on); a document is a hit when
+        its coverage reaches max(1, ceil(threshold * len(query)))."""
+        if type(self)._search_batch_call is not Search._search_batch_call:
+            raise CobsGpuError(_capi.ERR_UNSUPPORTED, "coverage: not on a device-list handle (the call has no counterpart there)")
+        qs = [q if type(q) is bytes else _as_bytes(q) for q in queries]
+        nq = len(qs)
+        arr = (C.c_char_p * max(nq, 1))(*qs)
+        lens = (C.c_size_t * max(nq, 1))(*[len(q) for q in qs])
+        offs = np.zeros(nq + 1, dtype=np.uint64)
+        bad = C.c_size_t(0)
+        if num_results > 0:
+            cap = nq * min(int(num_results), self.total_counts)
+        elif threshold <= 0:
+            cap = nq * self.total_counts
+        else:
+            # (a buffer that proves too small costs a second run of the whole call: sized by the hits per query of the
+            # earlier thresholded coverage calls on this handle)
+            cap = max(16 * nq, int(self.__dict__.get("_coverage_hits_per_query", 0.0) * nq * 1.25)) + 1024
+        cap = max(1, cap)
+        while True:
+            hits = np.zeros(cap, dtype=self.HIT_DTYPE)
+            st = self._lib.cobs_gpu_search_coverage(
+                self._h, arr, lens, nq, float(threshold), int(num_results), C.cast(hits.ctypes.data, C.POINTER(Hit)), cap,
+                C.cast(offs.ctypes.data, C.POINTER(C.c_size_t)), C.byref(bad))
+            if st == _capi.ERR_CAPACITY and int(offs[nq]) > cap:
+                cap = int(offs[nq])
+                continue
+            check(st)
+            break
+        if threshold > 0 and num_results == 0 and nq:
+            self._coverage_hits_per_query = max(int(offs[nq]) / nq, 0.95 * self.__dict__.get("_coverage_hits_per_query", 0.0))
+        return offs, hits[:int(offs[nq])]
+
+    def search_coverage(self, query, threshold=0.0, num_results=0):
+        """one query -> [SearchResult] in result order (doc_name, covered bases); a list or tuple of queries -> one such
+        list per query"""
+        many = isinstance(query, (list, tuple))
+        offs, hits = self.search_coverage_arrays(list(query) if many else [query], threshold, num_results)
+        rows = hits.tolist()
+        out = [[SearchResult(self.doc_name(f, d), sc) for (f, d, sc) in rows[int(offs[i]):int(offs[i + 1])]]
+               for i in range(len(offs) - 1)]
+        return out if many else out[0]
+
+    def coverage_ms(self):
+        """stage times of the coverage searches since the previous call of this method (HIP events, summed over passes)"""
+        t = (C.c_double * 3)()
+        check(self._lib.cobs_gpu_coverage_ms(self._h, C.byref(t)))
+        return {"hash_ms": t[0], "scan_ms": t[1], "passes": int(t[2])}
 
     # -- document sets: score a query against labelled groups of documents ----------
     SET_HIT_DTYPE = np.dtype([("file_no", "<u4"), ("set", "<u4"), ("any", "<u4"), ("all", "<u4")])

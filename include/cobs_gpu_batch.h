@@ -273,6 +273,43 @@ cobs_gpu_status cobs_gpu_search_sets(cobs_gpu_index* ix, const char* const* quer
                                      cobs_gpu_set_hit* hits, size_t cap, size_t* hit_offsets /* nq + 1 */,
                                      size_t* bad_query);
 
+/* ---- coverage search ------------------------------------------------------ */
+/* A search whose score is the number of query BASES covered by the k-mers a document holds, beyond the reference.  One
+ * substitution in a read removes the k k-mers that overlap it, but all other bases still lie inside a present k-mer.
+ *   File and query.  File f has term size k_f, the handle findere z, query q the length L = len(q).
+ *   Positions.       In file f the query has n = L - k_f + 1 - z positions.
+ *   Set position.    Position p is set in document d exactly as cobs_gpu_prevalence and cobs_gpu_hit_positions define it:
+ *                    terms p .. p + z are all present (the invalid-bases policy included, through K1's table).
+ *   Span.            span = k_f + z.
+ *   Covered bases.   A set position p covers bases p .. p + span - 1 of the query.  coverage(q, f, d) is the number of
+ *                    bases b in [0, L) covered by at least one set position of d: 0 .. L.
+ *   Bounds.          With s > 0 set positions: s + span - 1 <= coverage <= min(L, s * span).
+ *   Threshold.       For threshold > 0 a real document is a hit when coverage >= max(1, ceil(threshold * L)), computed
+ *                    in double.  For threshold <= 0 every real document is returned, coverage 0 included.
+ *   Invalid bases.   Under COBS_GPU_INVALID_MISS and _SKIP a position whose window holds a non-ACGT character is not set;
+ *                    the denominator stays L under both, so the two policies give the SAME result here, as they do for
+ *                    the weighted search.  Under _ERROR an invalid base fails the call as it does for a search.
+ *   Order.           Per query the records are ordered by coverage descending, then (file_no, doc) ascending, and cut to
+ *                    the first num_results when num_results > 0; the reference's index-order rule does NOT apply.
+ *                    hits[hit_offsets[q] .. hit_offsets[q+1]) belong to query q, `score` carries the coverage.
+ * Everything the host can refuse is refused before any device work: COBS_GPU_ERR_ARG (NULL arguments),
+ * COBS_GPU_ERR_QUERY_TOO_SHORT, COBS_GPU_ERR_QUERY_TOO_LONG for L >= 2^20 (*bad_query = the offending query),
+ * COBS_GPU_ERR_UNSUPPORTED when span > 255 in some file, on a handle opened with an HBM budget (its rows are not all
+ * resident) or as one shard of several.  The device list (cobs_gpu_multi_*) has no counterpart.
+ * COBS_GPU_ERR_INVALID_BASE comes from the device (*bad_query).  COBS_GPU_ERR_CAPACITY when cap is too small --
+ * hit_offsets then holds the needed sizes (hit_offsets[nq] the total), known from the one scan that ran (hits may be NULL
+ * when cap is 0).  COBS_GPU_ERR_HIP when the device has no room for the hit records of a pass.
+ * On the device: K1 and one scan that walks every document's positions in order with a bit-sliced countdown and appends
+ * the documents that pass to a pool; no score matrix exists.  cobs_gpu_coverage_ms (cobs_gpu_diag.h) reads the timers.
+ * cobs_gpu_covered_bases is the same count on the host, from one cobs_gpu_hit_positions bitmap of n positions (bit p of
+ * words[p / 64]; bits at or beyond n are ignored): for every hit of any search,
+ *   cobs_gpu_covered_bases(its bitmap, n, k_f + z) == the coverage cobs_gpu_search_coverage gives the document. */
+uint64_t cobs_gpu_covered_bases(const uint64_t* words, size_t n, uint32_t span);      /* host arithmetic, no device */
+cobs_gpu_status cobs_gpu_search_coverage(cobs_gpu_index* ix, const char* const* queries, const size_t* lens, size_t nq,
+                                         double threshold, size_t num_results,
+                                         cobs_gpu_hit* hits, size_t cap, size_t* hit_offsets /* nq + 1 */,
+                                         size_t* bad_query);
+
 /* score slots per query held by THIS shard (== cobs_gpu_total_counts when
  * unsharded); device count rows have this many elements */
 uint64_t cobs_gpu_local_counts(const cobs_gpu_index* ix);

@@ -93,6 +93,11 @@ cobs_gpu_status cobs_gpu_weighted_ms(cobs_gpu_index* ix, double out[5]);   /* ha
  * events), out[3] = the host's ordering of the records, out[4] = passes. */
 cobs_gpu_status cobs_gpu_sets_ms(cobs_gpu_index* ix, double out[5]);   /* hash, presence, select, ordering, passes; reset on read */
 
+/* HIP-event durations (ms) of the stages of the cobs_gpu_search_coverage calls on this handle since the previous call of
+ * this function, summed over their passes: out[0] = K1 (hashing), out[1] = the coverage scan (a scan repeated after a pool
+ * overflow included), out[2] = passes. */
+cobs_gpu_status cobs_gpu_coverage_ms(cobs_gpu_index* ix, double out[3]);   /* hash, scan, passes; reset on read */
+
 /* Durations (ms) of the LAST cobs_gpu_search_groups call on this handle: out[0] = the accumulate kernel (HIP events, summed
  * over the call's passes), out[1] = the select kernel (HIP events), out[2] = the host's ordering of the records. */
 cobs_gpu_status cobs_gpu_groups_ms(cobs_gpu_index* ix, double out[3]);

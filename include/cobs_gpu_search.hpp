@@ -52,6 +52,14 @@ public:
     cobs_gpu_status status;
 };
 
+//! The query bases covered by the set positions of one cobs_gpu_hit_positions bitmap of n positions (a set position
+//! covers span = term size + findere bases): what ClassicSearch::search_coverage scores the document with.  Host
+//! arithmetic (cobs_gpu_covered_bases); Error(COBS_GPU_ERR_ARG) when words is too short for n.
+inline uint64_t covered_bases(const std::vector<uint64_t>& words, size_t n, uint32_t span) {
+    if (n > words.size() * 64) throw Error(COBS_GPU_ERR_ARG, "covered_bases: words holds fewer than n positions");
+    return cobs_gpu_covered_bases(words.data(), n, span);
+}
+
 //! The reference's Search carries a public `Timer timer_` with an accessor `timer()` (cobs/query/search.hpp:35-46,
 //! cobs/util/timer.hpp:19-55) that its callers read and reset: `s.timer().print("search")` (src/cobs.cpp:468),
 //! `s.timer().reset()` and `cobs::Timer t = s.timer(); t.get("hashes") ...` in benchmark_fpr_run (:623, :644-661).
@@ -416,6 +424,33 @@ public:
         for (size_t q = 0; q < nq; ++q)
             for (size_t i = offs[q]; i < offs[q + 1]; ++i)
                 results[q].push_back(SetResult{hits[i].file_no, hits[i].set, hits[i].any, hits[i].all});
+    }
+
+    //! Coverage search (beyond the reference; cobs_gpu_search_coverage): a document scores the query bases that lie inside
+    //! a set position (term size + findere bases from the position on) and is a hit when that reaches
+    //! max(1, ceil(threshold * query length)); results[q] is ordered by coverage descending, then (file, document), and
+    //! SearchResult::score carries the covered bases.
+    void search_coverage(const std::vector<std::string>& queries, std::vector<std::vector<SearchResult>>& results,
+                         double threshold = 0.0, size_t num_results = 0) {
+        std::vector<const char*> qp;
+        std::vector<size_t> ql;
+        for (const auto& q : queries) { qp.push_back(q.data()); ql.push_back(q.size()); }
+        const size_t nq = queries.size();
+        std::vector<size_t> offs(nq + 1, 0);
+        std::vector<cobs_gpu_hit> hits(16 * nq + 1024);
+        size_t bad = 0;
+        cobs_gpu_status st;
+        for (;;) {
+            st = cobs_gpu_search_coverage(ix_, qp.data(), ql.data(), nq, threshold, num_results, hits.data(), hits.size(),
+                                          offs.data(), &bad);
+            if (st != COBS_GPU_ERR_CAPACITY || offs[nq] <= hits.size()) break;
+            hits.resize(offs[nq]);          // (the call reported the needed size)
+        }
+        check(st);
+        results.assign(nq, {});
+        for (size_t q = 0; q < nq; ++q)
+            for (size_t i = offs[q]; i < offs[q + 1]; ++i)
+                results[q].push_back(SearchResult(cobs_gpu_doc_name(ix_, hits[i].file_no, hits[i].doc), hits[i].score));
     }
 
     //! one document of a group's result: the sum of the scores of the group's queries and how many of them it was a hit of
