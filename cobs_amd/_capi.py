@@ -55,6 +55,10 @@ class SetHit(C.Structure):
     _fields_ = [("file_no", C.c_uint32), ("set", C.c_uint32), ("any", C.c_uint32), ("all", C.c_uint32)]
 
 
+class SetQuorumHit(C.Structure):
+    _fields_ = [("file_no", C.c_uint32), ("set", C.c_uint32), ("core", C.c_uint32), ("any", C.c_uint32)]
+
+
 class BuildParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("term_size", C.c_uint32), ("canonicalize", C.c_uint32),
                 ("num_hashes", C.c_uint32), ("false_positive_rate", C.c_double),
@@ -179,6 +183,11 @@ SYMBOLS = {
     "cobs_gpu_search_sets": (_int, [_vp, C.POINTER(_cp), C.POINTER(_sz), _sz, _dbl, _u32, _sz, C.POINTER(SetHit), _sz,
                                     C.POINTER(_sz), C.POINTER(_sz)]),
     "cobs_gpu_sets_ms": (_int, [_vp, C.POINTER(C.c_double * 5)]),
+    "cobs_gpu_search_sets_quorum": (_int, [_vp, C.POINTER(_cp), C.POINTER(_sz), _sz, _dbl, _dbl, _sz, C.POINTER(SetQuorumHit), _sz,
+                                           C.POINTER(_sz), C.POINTER(_sz)]),
+    "cobs_gpu_set_prevalence": (_int, [_vp, C.POINTER(_cp), C.POINTER(_sz), _sz, C.POINTER(_u32), _sz, C.POINTER(_sz),
+                                       C.POINTER(_sz), C.POINTER(_sz)]),
+    "cobs_gpu_set_quorum_ms": (_int, [_vp, C.POINTER(C.c_double * 5)]),
     "cobs_gpu_covered_bases": (_u64, [_pu64, _sz, _u32]),
     "cobs_gpu_search_coverage": (_int, [_vp, C.POINTER(_cp), C.POINTER(_sz), _sz, _dbl, _sz, C.POINTER(Hit), _sz,
                                         C.POINTER(_sz), C.POINTER(_sz)]),

@@ -32,7 +32,7 @@
 static void usage() {
     std::fprintf(stderr,
                  "usage: cobs_gpu_query -i INDEX [-i INDEX ...] [-t THRESHOLD] [-l LIMIT] "
-                 "[-d DEVICE[,DEVICE...]] [--hbm-budget GIB] [--findere Z] [--invalid-bases MODE] [--positions] [--prevalence] [--weighted] [--coverage] [--fpr-adjust] [--sets FILE.tsv [--sets-by any|all]] (QUERY | -f QUERY_FILE)\n"
+                 "[-d DEVICE[,DEVICE...]] [--hbm-budget GIB] [--findere Z] [--invalid-bases MODE] [--positions] [--prevalence] [--weighted] [--coverage] [--fpr-adjust] [--sets FILE.tsv [--sets-by any|all | --sets-quorum X | --sets-profile]] (QUERY | -f QUERY_FILE)\n"
                  "       cobs_gpu_query doc-stats INDEX [--fill-above X]\n"
                  "         one line per document: file, name, sub-index, S_p, bits set in its filter, fill = bits / S_p, fpr = fill^H\n"
                  "       --fpr-adjust: every result line gets expected_fp (the positions the document's fill alone is expected to\n"
@@ -65,6 +65,11 @@ static void usage() {
                  "        the sets that reach -t: any = the positions at least one member holds, all = the positions every\n"
                  "        member holds; ordered by --sets-by any|all (default any), cut by -l (honours --findere and\n"
                  "        --invalid-bases).  Not with several devices or --hbm-budget.\n"
+                 "       --sets FILE.tsv --sets-quorum X (0 < X <= 1): the soft core -- per query its *comment line, then\n"
+                 "        set_name<TAB>core<TAB>any<TAB>members for the sets that reach -t: core = the positions at least\n"
+                 "        max(1, ceil(X * members)) members hold; ordered by core, cut by -l.\n"
+                 "       --sets FILE.tsv --sets-profile: per query its *comment line, then per set one line\n"
+                 "        set_name<TAB>members<TAB>c0 c1 ... c(n-1), c_p = the members that hold position p of the query.\n"
                  "       --findere Z (0..7): a k-mer position scores only when Z + 1 consecutive k-mers are all present\n"
                  "        (findere, beyond `cobs query`: far fewer false-positive k-mers; a query needs k + Z characters)\n"
                  "       --invalid-bases error|miss|skip: a character outside ACGT fails the call (error, the default, as `cobs query`\n"
@@ -312,6 +317,65 @@ static void print_sets(cobs_gpu::ClassicSearch& s, const std::vector<std::string
     }
 }
 
+// members of every set of every file, [file][set number]
+static std::vector<std::vector<uint32_t>> set_members(cobs_gpu::ClassicSearch& s) {
+    const size_t nf = cobs_gpu_num_files(s.handle());
+    std::vector<std::vector<uint32_t>> members(nf);
+    for (size_t f = 0; f < nf; ++f) {
+        uint32_t n = 0;
+        if (cobs_gpu_get_doc_sets(s.handle(), f, &n, nullptr, 0) != COBS_GPU_OK) throw cobs_gpu::Error(COBS_GPU_ERR_ARG, cobs_gpu_last_error());
+        members[f].assign(n, 0);
+        if (n && cobs_gpu_get_doc_sets(s.handle(), f, &n, members[f].data(), n) != COBS_GPU_OK)
+            throw cobs_gpu::Error(COBS_GPU_ERR_ARG, cobs_gpu_last_error());
+    }
+    return members;
+}
+
+// --sets-quorum X: per query its comment line, then set_name, core, any, members
+static void print_sets_quorum(cobs_gpu::ClassicSearch& s, const std::vector<std::string>& queries, const std::vector<std::string>* comments,
+                              const std::vector<std::string>& names, double quorum, double threshold, size_t num_results) {
+    std::vector<std::vector<cobs_gpu::ClassicSearch::SetQuorumResult>> results;
+    s.search_sets_quorum(queries, results, quorum, threshold, num_results);
+    const std::vector<std::vector<uint32_t>> members = set_members(s);
+    for (size_t q = 0; q < queries.size(); ++q) {
+        if (comments) std::cout << (*comments)[q] << '\t' << results[q].size() << '\n';
+        for (const auto& r : results[q])
+            std::cout << names[r.set] << '\t' << r.core << '\t' << r.any << '\t' << members[r.file_no][r.set] << '\n';
+    }
+}
+
+// --sets-profile: per query its comment line, then per non-empty set of every labelled file: set_name, members, the counts
+static void print_sets_profile(cobs_gpu::ClassicSearch& s, const std::vector<std::string>& queries, const std::vector<std::string>* comments,
+                               const std::vector<std::string>& names) {
+    std::vector<uint32_t> counts;
+    std::vector<size_t> offs;
+    s.set_prevalence(queries, counts, offs);
+    const std::vector<std::vector<uint32_t>> members = set_members(s);
+    const size_t nf = members.size();
+    size_t lines = 0;
+    for (const auto& m : members) lines += (size_t)std::count_if(m.begin(), m.end(), [](uint32_t v) { return v != 0; });
+    std::string line;
+    for (size_t q = 0; q < queries.size(); ++q) {
+        if (comments) std::cout << (*comments)[q] << '\t' << lines << '\n';
+        for (size_t f = 0; f < nf; ++f) {
+            const size_t sets = (size_t)std::count_if(members[f].begin(), members[f].end(), [](uint32_t v) { return v != 0; });
+            if (sets == 0) continue;
+            const size_t n = (offs[q * nf + f + 1] - offs[q * nf + f]) / sets;
+            size_t at = offs[q * nf + f];
+            for (size_t c = 0; c < members[f].size(); ++c) {
+                if (members[f][c] == 0) continue;
+                line = names[c] + '\t' + std::to_string(members[f][c]) + '\t';
+                for (size_t i = 0; i < n; ++i) {
+                    if (i) line += ' ';
+                    line += std::to_string(counts[at + i]);
+                }
+                at += n;
+                std::cout << line << '\n';
+            }
+        }
+    }
+}
+
 // --fpr-adjust: "\texpected_fp\tadjusted" of every result of one query.  Under --invalid-bases skip the positions are the
 // query's valid ones per file, read from a device batch of that one query (cobs_gpu_batch_scored_positions).
 static std::vector<cobs_gpu::ClassicSearch::Adjusted> adjusted_of(cobs_gpu::ClassicSearch& s, const std::string& query,
@@ -412,6 +476,9 @@ int main(int argc, char** argv) {
     bool coverage = false;                   // --coverage
     bool fpr_adjust = false;                 // --fpr-adjust
     std::string sets_file, sets_by;          // --sets FILE.tsv, --sets-by any|all
+    std::string sets_quorum;                 // --sets-quorum X
+    bool have_quorum = false;
+    bool sets_profile = false;               // --sets-profile
     std::string group;                       // --group N|all
     double read_threshold = 0.0;             // --read-threshold X
     unsigned num_kmers = 1000, num_queries = 10000, num_warmup = 100;
@@ -475,6 +542,8 @@ int main(int argc, char** argv) {
         else if (a == "--fpr-adjust") fpr_adjust = true;
         else if (a == "--sets") sets_file = need("--sets");
         else if (a == "--sets-by") sets_by = need("--sets-by");
+        else if (a == "--sets-quorum") { sets_quorum = need("--sets-quorum"); have_quorum = true; }
+        else if (a == "--sets-profile") sets_profile = true;
         else if (a == "--group") group = need("--group");
         else if (a == "--read-threshold") read_threshold = std::atof(need("--read-threshold"));
         else if (a == "-h" || a == "--help") { usage(); return 0; }
@@ -507,6 +576,18 @@ int main(int argc, char** argv) {
     }
     if (!sets_by.empty() && sets_by != "any" && sets_by != "all") { std::fprintf(stderr, "--sets-by: any or all\n"); return 1; }
     if (!sets_by.empty() && sets_file.empty()) { std::fprintf(stderr, "--sets-by: needs --sets FILE.tsv\n"); return 1; }
+    double quorum = 0.0;
+    if (have_quorum) {
+        char* end = nullptr;
+        quorum = std::strtod(sets_quorum.c_str(), &end);
+        if (sets_quorum.empty() || *end != '\0' || !(quorum > 0.0 && quorum <= 1.0)) { std::fprintf(stderr, "--sets-quorum: a number in (0, 1]\n"); return 1; }
+        if (sets_file.empty()) { std::fprintf(stderr, "--sets-quorum: needs --sets FILE.tsv\n"); return 1; }
+        if (!sets_by.empty() || sets_profile) { std::fprintf(stderr, "--sets-quorum: not with --sets-by or --sets-profile\n"); return 1; }
+    }
+    if (sets_profile) {
+        if (sets_file.empty()) { std::fprintf(stderr, "--sets-profile: needs --sets FILE.tsv\n"); return 1; }
+        if (!sets_by.empty()) { std::fprintf(stderr, "--sets-profile: not with --sets-by\n"); return 1; }
+    }
     if (!sets_file.empty() && (devices.size() > 1 || force_sharded || hbm_budget != 0 || positions || prevalence || weighted ||
                                fpr_adjust || !group.empty())) {
         std::fprintf(stderr, "--sets: not with several devices (-d A,B / --sharded: any and all are not additive over shards) or "
@@ -610,7 +691,10 @@ int main(int argc, char** argv) {
         std::vector<std::string> set_names;
         if (!sets_file.empty()) label_doc_sets(dynamic_cast<cobs_gpu::ClassicSearch&>(s), set_rows, set_names);
         if (!query_line.empty() && !sets_file.empty()) {
-            print_sets(dynamic_cast<cobs_gpu::ClassicSearch&>(s), {query_line}, nullptr, set_names, threshold, sets_rank_by, num_results);
+            cobs_gpu::ClassicSearch& cs = dynamic_cast<cobs_gpu::ClassicSearch&>(s);
+            if (have_quorum) print_sets_quorum(cs, {query_line}, nullptr, set_names, quorum, threshold, num_results);
+            else if (sets_profile) print_sets_profile(cs, {query_line}, nullptr, set_names);
+            else print_sets(cs, {query_line}, nullptr, set_names, threshold, sets_rank_by, num_results);
             std::cout.flush();
             print_timer(s);
             return 0;
@@ -671,7 +755,10 @@ int main(int argc, char** argv) {
         }
         if (!query.empty()) { queries.push_back(query); comments.push_back(comment); }
         if (!sets_file.empty()) {
-            print_sets(dynamic_cast<cobs_gpu::ClassicSearch&>(s), queries, &comments, set_names, threshold, sets_rank_by, num_results);
+            cobs_gpu::ClassicSearch& cs = dynamic_cast<cobs_gpu::ClassicSearch&>(s);
+            if (have_quorum) print_sets_quorum(cs, queries, &comments, set_names, quorum, threshold, num_results);
+            else if (sets_profile) print_sets_profile(cs, queries, &comments, set_names);
+            else print_sets(cs, queries, &comments, set_names, threshold, sets_rank_by, num_results);
             std::cout.flush();
             print_timer(s);
             return 0;

@@ -16,37 +16,9 @@
 #include "engine.hpp"
 #include "prevalence_kernels.hpp"      // launch_prevalence_zero
 #include "set_kernels.hpp"
+#include "sets.hpp"                    // ChunkSegs, FileSets, SetsWork
 
 namespace cobs_amd {
-
-struct ChunkSegs {                          // the segment records of one resident chunk (set_kernels.hpp)
-    DevBuf<uint32_t> first;
-    DevBuf<uint4> mask;
-    DevBuf<uint32_t> set;
-    bool built = false;
-};
-
-struct FileSets {
-    std::vector<uint32_t> labels;           // [documents of the file]; empty: the file has no labels
-    uint32_t n_sets = 0;
-    std::vector<uint32_t> members;          // [n_sets]
-    std::vector<uint32_t> sets;             // the non-empty sets, ascending: the bitmaps' set index -> set number
-    std::vector<ChunkSegs> chunks;          // [Part::chunks]
-};
-
-struct SetsWork {
-    std::vector<FileSets> files;            // [parts]
-    DevBuf<uint32_t> bits;                  // any | miss of a pass
-    DevBuf<uint64_t> bm_off;
-    DevBuf<SetItem> items;
-    DevBuf<SetRec> pool;
-    DevBuf<unsigned long long> fill;
-    PinnedBuf<uint64_t> h_bm_off;
-    PinnedBuf<uint32_t> h_flags;            // K1's flag words | the pool's 64-bit fill
-    PhaseEvents<4> ev;                      // before K1 | presence | select | after it
-    double ms[4] = {0, 0, 0, 0};            // hash | presence | select | host ordering
-    uint64_t passes = 0;
-};
 
 void destroy_sets_work(SetsWork* w) { delete w; }
 

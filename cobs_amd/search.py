@@ -17,7 +17,7 @@ import sys
 import numpy as np
 
 from . import _capi
-from ._capi import CobsGpuError, GroupHit, Hit, IndexInfo, Options, SetHit, Synth, check
+from ._capi import CobsGpuError, GroupHit, Hit, IndexInfo, Options, SetHit, SetQuorumHit, Synth, check
 
 
 class SearchResult:
@@ -101,6 +101,27 @@ class SetResult:
     def __eq__(self, other):
         return (isinstance(other, SetResult) and (self.file_no, self.set, self.name, self.any, self.all) ==
                 (other.file_no, other.set, other.name, other.any, other.all))
+
+
+class SetQuorumResult:
+    """one set of documents of a quorum result (Search.search_sets_quorum): core = the positions of the query that at least
+    need = max(1, ceil(quorum * members)) members of the set hold, any = the positions at least one member holds; name = the
+    set's name (its number as text when the labels were given as numbers)"""
+    __slots__ = ("file_no", "set", "name", "core", "any")
+
+    def __init__(self, file_no=0, set=0, name="", core=0, any=0):
+        self.file_no = file_no
+        self.set = set
+        self.name = name
+        self.core = core
+        self.any = any
+
+    def __repr__(self):
+        return "SetQuorumResult(file_no=%d, set=%d, name=%r, core=%d, any=%d)" % (self.file_no, self.set, self.name, self.core, self.any)
+
+    def __eq__(self, other):
+        return (isinstance(other, SetQuorumResult) and (self.file_no, self.set, self.name, self.core, self.any) ==
+                (other.file_no, other.set, other.name, other.core, other.any))
 
 
 def doc_set_labels(labels, doc_names):
@@ -1012,6 +1033,90 @@ class Search:
         t = (C.c_double * 5)()
         check(self._lib.cobs_gpu_sets_ms(self._h, C.byref(t)))
         return {"hash_ms": t[0], "presence_ms": t[1], "select_ms": t[2], "order_ms": t[3], "passes": int(t[4])}
+
+    # -- document sets: the soft core of a set and the prevalence per set -----------
+    SET_QUORUM_HIT_DTYPE = np.dtype([("file_no", "<u4"), ("set", "<u4"), ("core", "<u4"), ("any", "<u4")])
+
+    def search_sets_quorum_arrays(self, queries, quorum, threshold=0.0, num_results=0):
+        """cobs_gpu_search_sets_quorum -> (offsets uint64 [nq + 1], hits SET_QUORUM_HIT_DTYPE): the records of query q are
+        hits[offsets[q]:offsets[q + 1]] -- one per non-empty set of every labelled file whose core (the positions at least
+        max(1, ceil(quorum * members)) members hold, 0 < quorum <= 1) reaches max(1, ceil(threshold * P)) --, by core
+        descending, then any descending, then (file_no, set)."""
+        self._sets_refuse_device_list()
+        qs = [q if type(q) is bytes else _as_bytes(q) for q in queries]
+        nq = len(qs)
+        arr = (C.c_char_p * max(nq, 1))(*qs)
+        lens = (C.c_size_t * max(nq, 1))(*[len(q) for q in qs])
+        offs = np.zeros(nq + 1, dtype=np.uint64)
+        bad = C.c_size_t(0)
+        per_query = sum(int(np.count_nonzero(self.doc_sets(f)[1])) for f in range(self.num_files))
+        cap = max(1, nq * (min(int(num_results), per_query) if num_results > 0 else per_query))
+        while True:
+            hits = np.zeros(cap, dtype=self.SET_QUORUM_HIT_DTYPE)
+            st = self._lib.cobs_gpu_search_sets_quorum(
+                self._h, arr, lens, nq, float(threshold), float(quorum), int(num_results),
+                C.cast(hits.ctypes.data, C.POINTER(SetQuorumHit)), cap, C.cast(offs.ctypes.data, C.POINTER(C.c_size_t)), C.byref(bad))
+            if st == _capi.ERR_CAPACITY and int(offs[nq]) > cap:
+                cap = int(offs[nq])
+                continue
+            check(st)
+            break
+        return offs, hits[:int(offs[nq])]
+
+    def search_sets_quorum(self, query, quorum, threshold=0.0, num_results=0):
+        """-> one list per query of SetQuorumResult(file_no, set, name, core, any) in result order; one str / bytes query ->
+        its list"""
+        single = isinstance(query, (str, bytes, bytearray))
+        qs = [query] if single else list(query)
+        offs, hits = self.search_sets_quorum_arrays(qs, quorum, threshold, num_results)
+        names = {f: self.doc_sets(f)[0] for f in range(self.num_files)}
+        rows = hits.tolist()
+        out = [[SetQuorumResult(f, s, names[f][s], c, a) for (f, s, c, a) in rows[int(offs[q]):int(offs[q + 1])]] for q in range(len(qs))]
+        return out[0] if single else out
+
+    def set_prevalence_arrays(self, queries):
+        """cobs_gpu_set_prevalence -> (offsets uint64 [nq * num_files + 1], counts uint32): segment (q, f) is
+        counts[offsets[q * num_files + f]:offsets[q * num_files + f + 1]], the file's non-empty sets (ascending set number) x
+        the n = T_f - findere positions of query q, set-major: how many members of the set hold the position.  A file
+        without labels has an empty segment."""
+        self._sets_refuse_device_list()
+        qs = [q if type(q) is bytes else _as_bytes(q) for q in queries]
+        nq = len(qs)
+        arr = (C.c_char_p * max(nq, 1))(*qs)
+        lens = (C.c_size_t * max(nq, 1))(*[len(q) for q in qs])
+        offsets = np.zeros(nq * self.num_files + 1, dtype=np.uint64)
+        need, bad = C.c_size_t(0), C.c_size_t(0)
+        # the number of cells is host arithmetic (the call refuses a buffer that is too small before any device work)
+        counts = np.zeros(0, dtype=np.uint32)
+        while True:
+            st = self._lib.cobs_gpu_set_prevalence(
+                self._h, arr, lens, nq, C.cast(counts.ctypes.data, C.POINTER(C.c_uint32)), counts.size,
+                C.cast(offsets.ctypes.data, C.POINTER(C.c_size_t)), C.byref(need), C.byref(bad))
+            if st == _capi.ERR_CAPACITY and need.value > counts.size:
+                counts = np.zeros(need.value, dtype=np.uint32)
+                continue
+            check(st)
+            break
+        return offsets, counts
+
+    def set_prevalence(self, query):
+        """per query a list with one uint32 array [non-empty sets, n] per file (set_prevalence_arrays, cut up; row c belongs to
+        the c-th set with members, ascending set number); one str / bytes query -> its list"""
+        single = isinstance(query, (str, bytes, bytearray))
+        qs = [query] if single else list(query)
+        offsets, counts = self.set_prevalence_arrays(qs)
+        nf = self.num_files
+        nsets = [int(np.count_nonzero(self.doc_sets(f)[1])) for f in range(nf)]
+        out = [[counts[int(offsets[q * nf + f]):int(offsets[q * nf + f + 1])].reshape(nsets[f], -1) if nsets[f] else
+                np.zeros((0, 0), dtype=np.uint32) for f in range(nf)] for q in range(len(qs))]
+        return out[0] if single else out
+
+    def set_quorum_ms(self):
+        """stage times of the quorum searches and set prevalences since the previous call of this method (HIP events, summed
+        over passes; the ordering on the host clock)"""
+        t = (C.c_double * 5)()
+        check(self._lib.cobs_gpu_set_quorum_ms(self._h, C.byref(t)))
+        return {"hash_ms": t[0], "count_ms": t[1], "select_ms": t[2], "order_ms": t[3], "passes": int(t[4])}
 
     # -- grouped search: which documents a SET of queries comes from -----------------
     GROUP_HIT_DTYPE = np.dtype([("file_no", "<u4"), ("doc", "<u4"), ("score", "<u4"), ("votes", "<u4")])

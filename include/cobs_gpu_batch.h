@@ -273,6 +273,51 @@ cobs_gpu_status cobs_gpu_search_sets(cobs_gpu_index* ix, const char* const* quer
                                      cobs_gpu_set_hit* hits, size_t cap, size_t* hit_offsets /* nq + 1 */,
                                      size_t* bad_query);
 
+/* ---- document sets: quorum and per-set prevalence -------------------------- */
+/* The soft core of a set and the frequency of a stretch per set, beyond the reference.  `all` of cobs_gpu_search_sets is
+ * brittle -- one fragmented assembly among 5 000 zeroes a position --, so pan-genome tools score the positions that at least
+ * 95 % or 99 % of a set's members hold, and report how many members of every set hold a position: cobs_gpu_prevalence split
+ * by set.  Position, n = T - z, "set in document d", the denominator P and the invalid-bases policies are exactly those of
+ * cobs_gpu_search_sets and cobs_gpu_prevalence; the labels are those of cobs_gpu_set_doc_sets.  For file f with labels let c
+ * range over the file's non-empty sets in ascending set number, members(f, c) = the real documents of f labelled c:
+ *   count(q, f, c, p) = the members of c in which position p of query q is set.  Padding slots, slots >= D_f and unlabelled
+ *                       documents never count, whatever bits the file holds there; under COBS_GPU_INVALID_MISS / _SKIP a
+ *                       position whose window holds a character outside ACGT is 0.
+ *   need(f, c)        = max(1, ceil(quorum * members(f, c))) for 0 < quorum <= 1, computed on the host in double, once per
+ *                       set and call (the device never multiplies by quorum); any other quorum, NaN included, is
+ *                       COBS_GPU_ERR_ARG.
+ *   core(q, f, c)     = the positions p < n with count >= need(f, c);  any(q, f, c) = the positions with count > 0.
+ *                       quorum = 1 gives core = `all` of cobs_gpu_search_sets; a quorum small enough that need = 1 gives
+ *                       core = its `any`.
+ * cobs_gpu_search_sets_quorum: a set is a hit when core >= max(1, ceil(threshold * P)), computed in double; P = 0 returns
+ * nothing; threshold <= 0 returns every non-empty set of every labelled file.  Per query the records are ordered by core
+ * descending, then any descending, then (file_no, set) ascending, and cut to num_results when it is > 0.
+ * hits[hit_offsets[q] .. hit_offsets[q+1]) belong to query q.  COBS_GPU_ERR_CAPACITY when cap is too small -- hit_offsets
+ * then holds the needed sizes (hit_offsets[nq] the total; hits may be NULL when cap is 0).
+ * cobs_gpu_set_prevalence: segment (q, f) = counts[offsets[q * n_files + f] .. offsets[q * n_files + f + 1]) holds
+ * nonempty_sets(f) * n(q, f) counts, set-major: the c-th non-empty set in ascending set number (the order
+ * cobs_gpu_get_doc_sets implies) has its position p at offsets[q * n_files + f] + c * n + p.  A file without labels has an
+ * empty segment.  COBS_GPU_ERR_CAPACITY when cap is too small -- offsets and *needed (optional) are filled, so the call can
+ * be repeated (counts may be NULL when cap is 0); the sizes are host arithmetic, nothing has run.
+ * Both refuse before any device work: COBS_GPU_ERR_ARG (NULL arguments, a bad quorum), COBS_GPU_ERR_QUERY_TOO_SHORT /
+ * _TOO_LONG (*bad_query = the offending query), COBS_GPU_ERR_UNSUPPORTED on a handle opened with an HBM budget or as one
+ * shard of several (the counts are additive over shards, but nothing adds them up yet; the mirrors also refuse on the device
+ * list), COBS_GPU_ERR_HIP, with the sizes in the message, when the counts of a single query -- 4 bytes per (set, position),
+ * 16 times the two bitmaps of cobs_gpu_search_sets -- do not fit the pass workspace (tuning key pass_bytes).
+ * COBS_GPU_ERR_INVALID_BASE comes from the device (*bad_query).
+ * On the device: K1, a kernel that zeroes the cells, a count kernel that reduces the prevalence kernel's gather over the
+ * columns of one set at a time (from inverse segment records, built from the labels on the first of these calls and
+ * dropped when the labels are replaced or cleared), and for the search a select kernel over the counts; passes are cut by
+ * pass_bytes and the results do not depend on the cut.  cobs_gpu_set_quorum_ms (cobs_gpu_diag.h) reads the stage timers. */
+typedef struct cobs_gpu_set_quorum_hit { uint32_t file_no, set, core, any; } cobs_gpu_set_quorum_hit;   /* 16 bytes */
+cobs_gpu_status cobs_gpu_search_sets_quorum(cobs_gpu_index* ix, const char* const* queries, const size_t* lens, size_t nq,
+                                            double threshold, double quorum, size_t num_results,
+                                            cobs_gpu_set_quorum_hit* hits, size_t cap, size_t* hit_offsets /* nq + 1 */,
+                                            size_t* bad_query);
+cobs_gpu_status cobs_gpu_set_prevalence(cobs_gpu_index* ix, const char* const* queries, const size_t* lens, size_t nq,
+                                        uint32_t* counts, size_t cap, size_t* offsets /* nq * n_files + 1 */, size_t* needed,
+                                        size_t* bad_query);
+
 /* ---- coverage search ------------------------------------------------------ */
 /* A search whose score is the number of query BASES covered by the k-mers a document holds, beyond the reference.  One
  * substitution in a read removes the k k-mers that overlap it, but all other bases still lie inside a present k-mer.

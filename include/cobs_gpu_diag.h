@@ -93,6 +93,12 @@ cobs_gpu_status cobs_gpu_weighted_ms(cobs_gpu_index* ix, double out[5]);   /* ha
  * events), out[3] = the host's ordering of the records, out[4] = passes. */
 cobs_gpu_status cobs_gpu_sets_ms(cobs_gpu_index* ix, double out[5]);   /* hash, presence, select, ordering, passes; reset on read */
 
+/* Durations (ms) of the stages of the cobs_gpu_search_sets_quorum and cobs_gpu_set_prevalence calls on this handle since the
+ * previous call of this function, summed over their passes: out[0] = K1 (hashing), out[1] = the set count kernel, out[2] =
+ * the quorum select kernel (HIP events; 0 for cobs_gpu_set_prevalence), out[3] = the host's ordering of the records,
+ * out[4] = passes. */
+cobs_gpu_status cobs_gpu_set_quorum_ms(cobs_gpu_index* ix, double out[5]);   /* hash, count, select, ordering, passes; reset on read */
+
 /* HIP-event durations (ms) of the stages of the cobs_gpu_search_coverage calls on this handle since the previous call of
  * this function, summed over their passes: out[0] = K1 (hashing), out[1] = the coverage scan (a scan repeated after a pool
  * overflow included), out[2] = passes. */

@@ -426,6 +426,57 @@ public:
                 results[q].push_back(SetResult{hits[i].file_no, hits[i].set, hits[i].any, hits[i].all});
     }
 
+    //! one set of documents of a quorum result: the positions at least need(set) members hold, and the positions at least
+    //! one member holds
+    struct SetQuorumResult {
+        uint32_t file_no, set, core, any;
+    };
+
+    //! the soft core of every non-empty set of every labelled file (cobs_gpu_search_sets_quorum): results[q] holds the sets
+    //! whose core -- the positions at least max(1, ceil(quorum * members)) members hold, 0 < quorum <= 1 -- reaches
+    //! max(1, ceil(threshold * P)), by core descending, then any descending, then (file, set)
+    void search_sets_quorum(const std::vector<std::string>& queries, std::vector<std::vector<SetQuorumResult>>& results,
+                            double quorum, double threshold = 0.0, size_t num_results = 0) {
+        std::vector<const char*> qp;
+        std::vector<size_t> ql;
+        for (const auto& q : queries) { qp.push_back(q.data()); ql.push_back(q.size()); }
+        const size_t nq = queries.size();
+        std::vector<size_t> offs(nq + 1, 0);
+        std::vector<cobs_gpu_set_quorum_hit> hits(16 * nq + 1024);
+        size_t bad = 0;
+        cobs_gpu_status st;
+        for (;;) {
+            st = cobs_gpu_search_sets_quorum(ix_, qp.data(), ql.data(), nq, threshold, quorum, num_results, hits.data(),
+                                             hits.size(), offs.data(), &bad);
+            if (st != COBS_GPU_ERR_CAPACITY || offs[nq] <= hits.size()) break;
+            hits.resize(offs[nq]);          // (the call reported the needed size)
+        }
+        check(st);
+        results.assign(nq, {});
+        for (size_t q = 0; q < nq; ++q)
+            for (size_t i = offs[q]; i < offs[q + 1]; ++i)
+                results[q].push_back(SetQuorumResult{hits[i].file_no, hits[i].set, hits[i].core, hits[i].any});
+    }
+
+    //! how many members of every set hold each position of every query (cobs_gpu_set_prevalence): segment (q, f) is
+    //! counts[offsets[q * n_files + f] .. offsets[q * n_files + f + 1]), the file's non-empty sets (ascending set number) x
+    //! the query's n = T_f - z positions, set-major; empty for a file without labels
+    void set_prevalence(const std::vector<std::string>& queries, std::vector<uint32_t>& counts, std::vector<size_t>& offsets) {
+        std::vector<const char*> qp;
+        std::vector<size_t> ql;
+        for (const auto& q : queries) { qp.push_back(q.data()); ql.push_back(q.size()); }
+        const size_t nq = queries.size();
+        offsets.assign(nq * cobs_gpu_num_files(ix_) + 1, 0);
+        counts.clear();
+        size_t bad = 0, need = 0;
+        cobs_gpu_status st = cobs_gpu_set_prevalence(ix_, qp.data(), ql.data(), nq, nullptr, 0, offsets.data(), &need, &bad);
+        if (st == COBS_GPU_ERR_CAPACITY && need > 0) {       // the size is host arithmetic: nothing has run yet
+            counts.resize(need);
+            st = cobs_gpu_set_prevalence(ix_, qp.data(), ql.data(), nq, counts.data(), counts.size(), offsets.data(), &need, &bad);
+        }
+        check(st);
+    }
+
     //! Coverage search (beyond the reference; cobs_gpu_search_coverage): a document scores the query bases that lie inside
     //! a set position (term size + findere bases from the position on) and is a hit when that reaches
     //! max(1, ceil(threshold * query length)); results[q] is ordered by coverage descending, then (file, document), and
