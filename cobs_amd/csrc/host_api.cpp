@@ -114,6 +114,7 @@ static cobs_gpu_status host_pass_begin(cobs_gpu_index* ix, int slot, const char*
             HIP_TRY(hipEventRecord(b->graph_t1, b->own_stream));
             b->graph_run = true;
             b->run_seq++;
+            b->read_seq = b->run_seq;        // no events of this run: cobs_gpu_batch_kernel_ms starts behind it
             b->ran = true;
             ix->graph_replays++;
             HIP_TRY(hipEventRecord(b->done, b->own_stream));
@@ -152,6 +153,10 @@ static cobs_gpu_status host_pass_begin(cobs_gpu_index* ix, int slot, const char*
                     if (ce != hipSuccess) cs = COBS_GPU_ERR_HIP;
                 }
                 const hipError_t ee = hipStreamEndCapture(b->own_stream, &graph);
+                // the ring slot of the captured run holds events recorded INSIDE the capture (no timestamps): the next plain
+                // pass must not read them -- cobs_gpu_batch_kernel_ms failed over that slot, its HIP error replaced the
+                // message of the pass, and the timers lost every plain pass until the ring had moved past the slot
+                b->read_seq = b->run_seq;
                 hipGraphExec_t exec = nullptr;
                 if (cs == COBS_GPU_OK && ee == hipSuccess && graph &&
                     hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess) {
@@ -240,6 +245,9 @@ static cobs_gpu_status host_pass_end(cobs_gpu_index* ix, int slot, double thresh
     }
     if (st == COBS_GPU_OK || st == COBS_GPU_ERR_INVALID_BASE) {
         float sm = 0, hm = 0;
+        // booking the timers never replaces the message of the pass ("Invalid DNA base pair ... (query i)" of a
+        // cobs_gpu_counts call): whatever the timer readers report is dropped below
+        const std::string keep = last_error_text();
         // (a replayed graph re-records the events of the run it was captured from: no per-kernel split)
         if (b->ran && !b->graph_run && cobs_gpu_batch_kernel_ms(b, &sm, &hm) == COBS_GPU_OK) {
             ix->timers[0] += hm * 1e-3;
@@ -249,6 +257,7 @@ static cobs_gpu_status host_pass_end(cobs_gpu_index* ix, int slot, double thresh
         } else {
             (void)hipGetLastError();
         }
+        last_error_text() = keep;
     }
     return st;
 }

@@ -316,6 +316,30 @@ def test_graph_replay_gets_each_query_its_own_threshold(gpu_lib, data):
 
 
 @_gpu
+def test_counts_after_a_captured_search_names_the_invalid_query(gpu_lib, data):
+    """the pair the call-sequence walk found (tests/test_gpu_call_sequence.py: search_small -> counts): a search captured
+    into a graph leaves a run in the batch's timer ring whose events were recorded inside the capture; booking the timers
+    of the next plain pass failed over them and replaced the message of cobs_gpu_counts' invalid base with a HIP error"""
+    from cobs_amd import _capi
+    path, fb = data["c1"]
+    clean = data["src"][900:1030]
+    s = gpu_lib.Search(path)
+    replays = s.graph_replays
+    for _ in range(3):                                  # candidate, capture, replay
+        assert s.search_hits([clean], 0.8, 0) == [F.results([fb], clean, 0, 0.8, 0)]
+    assert s.graph_replays > replays
+    s.timers(reset=True)
+    with pytest.raises(gpu_lib.CobsGpuError) as e:
+        s.counts(V.with_n(clean, [40]))
+    assert e.value.status == _capi.ERR_INVALID_BASE and "Invalid DNA base pair" in str(e.value) and "(query 0)" in str(e.value)
+    assert np.array_equal(s.counts(clean), F.counts([fb], clean, 0))        # the handle still answers
+    # ... and the plain passes behind the captured one are booked (only they have a hashing time of their own)
+    t = s.timers()
+    assert t["hashes"] > 0 and t["scan"] > 0, t
+    s.close()
+
+
+@_gpu
 def test_multi_file_handle(gpu_lib, data):
     names = ("c1", "p3", "c2k20")
     paths, files = [data[n][0] for n in names], [data[n][1] for n in names]
