@@ -192,6 +192,10 @@ SYMBOLS = {
     "cobs_gpu_search_coverage": (_int, [_vp, C.POINTER(_cp), C.POINTER(_sz), _sz, _dbl, _sz, C.POINTER(Hit), _sz,
                                         C.POINTER(_sz), C.POINTER(_sz)]),
     "cobs_gpu_coverage_ms": (_int, [_vp, C.POINTER(C.c_double * 3)]),
+    "cobs_gpu_best_window": (_u32, [_pu64, _sz, _u32, C.POINTER(_sz)]),
+    "cobs_gpu_search_window": (_int, [_vp, C.POINTER(_cp), C.POINTER(_sz), _sz, _u32, _dbl, _sz, C.POINTER(Hit), _sz,
+                                      C.POINTER(_sz), C.POINTER(_sz)]),
+    "cobs_gpu_window_ms": (_int, [_vp, C.POINTER(C.c_double * 3)]),
     "cobs_gpu_search_groups": (_int, [_vp, C.POINTER(_cp), C.POINTER(_sz), _sz, C.POINTER(_sz), _sz, _dbl, _dbl, _sz,
                                       C.POINTER(GroupHit), _sz, C.POINTER(_sz), _pu64, C.POINTER(_sz)]),
     "cobs_gpu_groups_ms": (_int, [_vp, C.POINTER(C.c_double * 3)]),

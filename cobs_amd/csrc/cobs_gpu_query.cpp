@@ -32,7 +32,7 @@
 static void usage() {
     std::fprintf(stderr,
                  "usage: cobs_gpu_query -i INDEX [-i INDEX ...] [-t THRESHOLD] [-l LIMIT] "
-                 "[-d DEVICE[,DEVICE...]] [--hbm-budget GIB] [--findere Z] [--invalid-bases MODE] [--positions] [--prevalence] [--weighted] [--coverage] [--fpr-adjust] [--sets FILE.tsv [--sets-by any|all | --sets-quorum X | --sets-profile]] (QUERY | -f QUERY_FILE)\n"
+                 "[-d DEVICE[,DEVICE...]] [--hbm-budget GIB] [--findere Z] [--invalid-bases MODE] [--positions] [--prevalence] [--weighted] [--coverage] [--window N] [--fpr-adjust] [--sets FILE.tsv [--sets-by any|all | --sets-quorum X | --sets-profile]] (QUERY | -f QUERY_FILE)\n"
                  "       cobs_gpu_query doc-stats INDEX [--fill-above X]\n"
                  "         one line per document: file, name, sub-index, S_p, bits set in its filter, fill = bits / S_p, fpr = fill^H\n"
                  "       --fpr-adjust: every result line gets expected_fp (the positions the document's fill alone is expected to\n"
@@ -59,6 +59,12 @@ static void usage() {
                  "        length: a read with one substitution keeps all but one of its bases; same output as a plain query\n"
                  "        with the covered bases in place of the count (honours -l, --findere and --invalid-bases).  Not with\n"
                  "        several devices or --hbm-budget.\n"
+                 "       --window N: window search -- a document scores the most positions it holds in any N (1 .. 4095) consecutive\n"
+                 "        positions of the query and is a hit when that reaches -t of N (of the query's positions, if fewer): for a\n"
+                 "        long query whose documents hold a stretch of it; same output as --coverage with that number as the score\n"
+                 "        (honours -l, --findere and --invalid-bases); with --positions every line also gets the 0/1 string and the\n"
+                 "        window's first start.  Not with several devices, --hbm-budget, --coverage, --prevalence, --weighted,\n"
+                 "        --sets, --group or --fpr-adjust.\n"
                  "       --sets FILE.tsv: score every query against SETS of documents; the file holds lines\n"
                  "        document name<TAB>set name (a document it does not name is in no set; a name the index does not hold\n"
                  "        is an error).  Per query its *comment line (with the number of sets), then set_name<TAB>any<TAB>all for\n"
@@ -219,6 +225,28 @@ static void print_with_positions(cobs_gpu::ClassicSearch& s, const std::vector<s
         for (size_t i = 0; i < results[q].size(); ++i)
             std::cout << results[q][i].doc_name << '\t' << results[q][i].score << '\t'
                       << position_string(pos[q][i], npos[q][i]) << (fpr_adjust ? adjusted_columns(adj[i]) : std::string()) << '\n';
+    }
+}
+
+// --window: the lines of --coverage with the best window's count as the score; with --positions every line gets the 0/1
+// string of --positions and the first start of a window that reaches the score (cobs_gpu_best_window over the bitmap)
+static void print_window(cobs_gpu::ClassicSearch& s, const std::vector<std::string>& queries, const std::vector<std::string>* comments,
+                         uint32_t window, double threshold, size_t num_results, bool positions) {
+    std::vector<std::vector<cobs_gpu::SearchResult>> results;
+    std::vector<std::vector<std::vector<uint64_t>>> pos;
+    std::vector<std::vector<size_t>> npos;
+    s.search_window(queries, window, results, threshold, num_results, positions ? &pos : nullptr, positions ? &npos : nullptr);
+    for (size_t q = 0; q < queries.size(); ++q) {
+        if (comments) std::cout << (*comments)[q] << '\t' << results[q].size() << '\n';
+        for (size_t i = 0; i < results[q].size(); ++i) {
+            std::cout << results[q][i].doc_name << '\t' << results[q][i].score;
+            if (positions) {
+                size_t start = 0;
+                (void)cobs_gpu::best_window(pos[q][i], npos[q][i], window, &start);
+                std::cout << '\t' << position_string(pos[q][i], npos[q][i]) << '\t' << start;
+            }
+            std::cout << '\n';
+        }
     }
 }
 
@@ -474,6 +502,7 @@ int main(int argc, char** argv) {
     bool prevalence = false;                 // --prevalence
     bool weighted = false;                   // --weighted
     bool coverage = false;                   // --coverage
+    std::string window_arg;                  // --window N
     bool fpr_adjust = false;                 // --fpr-adjust
     std::string sets_file, sets_by;          // --sets FILE.tsv, --sets-by any|all
     std::string sets_quorum;                 // --sets-quorum X
@@ -539,6 +568,7 @@ int main(int argc, char** argv) {
         else if (a == "--prevalence") prevalence = true;
         else if (a == "--weighted") weighted = true;
         else if (a == "--coverage") coverage = true;
+        else if (a == "--window") window_arg = need("--window");
         else if (a == "--fpr-adjust") fpr_adjust = true;
         else if (a == "--sets") sets_file = need("--sets");
         else if (a == "--sets-by") sets_by = need("--sets-by");
@@ -567,6 +597,19 @@ int main(int argc, char** argv) {
                              "--hbm-budget (the rows have to be resident on one GPU), nor with --positions, --prevalence, "
                              "--fpr-adjust or --group\n");
         return 1;
+    }
+    uint32_t window = 0;
+    if (!window_arg.empty()) {
+        char* end = nullptr;
+        const unsigned long long n = std::strtoull(window_arg.c_str(), &end, 10);
+        if (*end != '\0' || n == 0 || n > 4095) { std::fprintf(stderr, "--window: a number of positions, 1 .. 4095\n"); return 1; }
+        window = (uint32_t)n;
+        if (devices.size() > 1 || force_sharded || hbm_budget != 0 || coverage || prevalence || weighted || fpr_adjust || !group.empty() ||
+            !sets_file.empty()) {
+            std::fprintf(stderr, "--window: not with several devices (-d A,B / --sharded) or --hbm-budget (the rows have to be "
+                                 "resident on one GPU), nor with --coverage, --prevalence, --weighted, --sets, --fpr-adjust or --group\n");
+            return 1;
+        }
     }
     if (coverage && (devices.size() > 1 || force_sharded || hbm_budget != 0 || positions || prevalence || weighted || fpr_adjust ||
                      !group.empty() || !sets_file.empty())) {
@@ -713,6 +756,12 @@ int main(int argc, char** argv) {
             print_timer(s);
             return 0;
         }
+        if (!query_line.empty() && window) {
+            print_window(dynamic_cast<cobs_gpu::ClassicSearch&>(s), {query_line}, nullptr, window, threshold, num_results, positions);
+            std::cout.flush();
+            print_timer(s);
+            return 0;
+        }
         if (!query_line.empty() && weighted) {
             std::vector<std::vector<cobs_gpu::SearchResult>> results;
             dynamic_cast<cobs_gpu::ClassicSearch&>(s).search_weighted({query_line}, results, threshold, num_results);
@@ -776,6 +825,12 @@ int main(int argc, char** argv) {
                 std::cout << comments[q] << '\t' << results[q].size() << '\n';
                 for (const auto& r : results[q]) std::cout << r.doc_name << '\t' << r.score << '\n';
             }
+            std::cout.flush();
+            print_timer(s);
+            return 0;
+        }
+        if (window) {
+            print_window(dynamic_cast<cobs_gpu::ClassicSearch&>(s), queries, &comments, window, threshold, num_results, positions);
             std::cout.flush();
             print_timer(s);
             return 0;

@@ -78,6 +78,7 @@ Tuning Tuning::from_env() {
     if (const char* e = getenv("COBS_GPU_STREAM_BUF_KIB")) t.stream_buf_kib = (uint32_t)std::strtoul(e, nullptr, 0);
     if (const char* e = getenv("COBS_GPU_IDX64")) t.idx64 = atoi(e) != 0;
     if (const char* e = getenv("COBS_GPU_COVERAGE_SEG")) t.coverage_seg = (uint32_t)std::min<unsigned long>(std::strtoul(e, nullptr, 0), (1ul << 20) - 1);
+    if (const char* e = getenv("COBS_GPU_WINDOW_SEG")) t.window_seg = (uint32_t)std::min<unsigned long>(std::strtoul(e, nullptr, 0), (1ul << 20) - 1);
     if (const char* e = getenv("COBS_GPU_EXP")) t.exp = (uint32_t)std::strtoul(e, nullptr, 0);      // A/B variants, also under the test suite
     return t;
 }
@@ -164,6 +165,7 @@ cobs_gpu_index::~cobs_gpu_index() {
     if (weighted) destroy_weighted_work(weighted);
     if (sets) destroy_sets_work(sets);
     if (coverage) destroy_coverage_work(coverage);
+    if (window) destroy_window_work(window);
     for (auto* b : scratch) delete b;
     if (xchg_stream) (void)hipStreamDestroy(xchg_stream);
 }

@@ -155,6 +155,7 @@ struct Tuning {
     uint32_t phase_slots = 0;   // tuning builds (make timing): work-groups of a scan launch that record phase stamps
     bool idx64 = false;         // COBS_GPU_IDX64: every part keeps 64-bit row indices in K1's table (tests: the wide table on a small index)
     uint32_t coverage_seg = 0;  // COBS_GPU_COVERAGE_SEG (tests): positions per segment of the coverage scan (0: by query length)
+    uint32_t window_seg = 0;    // COBS_GPU_WINDOW_SEG (tests): positions per segment of the window scan (0: by window and query length)
     uint64_t hit_cap = 0;       // tests: at most this many records in a batch's hit pool (0 = its full capacity); lowers the
                                 // cap the kernels honour, never the allocation -- small fixtures reach the overflow paths
     static Tuning from_env();
@@ -304,6 +305,7 @@ struct PrevalenceWork;  // prevalence.cpp: buffers of cobs_gpu_prevalence
 struct WeightedWork;    // weighted.cpp: cells, weights and hit pool of cobs_gpu_search_weighted
 struct SetsWork;        // sets.cpp: labels, segment records and bitmaps of cobs_gpu_search_sets
 struct CoverageWork;    // coverage.cpp: thresholds and hit pool of cobs_gpu_search_coverage
+struct WindowWork;      // window.cpp: thresholds, windows and hit pool of cobs_gpu_search_window
 
 }  // namespace cobs_amd
 
@@ -332,6 +334,7 @@ struct cobs_gpu_index {
     cobs_amd::WeightedWork* weighted = nullptr;     // weighted.cpp
     cobs_amd::SetsWork* sets = nullptr;             // sets.cpp
     cobs_amd::CoverageWork* coverage = nullptr;     // coverage.cpp
+    cobs_amd::WindowWork* window = nullptr;         // window.cpp
     ~cobs_gpu_index();
 };
 
@@ -573,6 +576,7 @@ void destroy_prevalence_work(PrevalenceWork* w);   // prevalence.cpp
 void destroy_weighted_work(WeightedWork* w);       // weighted.cpp
 void destroy_sets_work(SetsWork* w);               // sets.cpp
 void destroy_coverage_work(CoverageWork* w);       // coverage.cpp
+void destroy_window_work(WindowWork* w);           // window.cpp
 void drop_fill_cache(cobs_gpu_index* ix, size_t file_no);   // ... the cached counts of one file (its bits changed)
 bool rank_on_device_applies(const cobs_gpu_batch* b, size_t nq);
 cobs_gpu_status rank_launch(cobs_gpu_batch* b, size_t q_first, size_t nq, size_t limit);

@@ -236,6 +236,23 @@ def covered_bases(words, n, span):
     return int(_capi.load().cobs_gpu_covered_bases(C.cast(w.ctypes.data, C.POINTER(C.c_uint64)), n, int(span)))
 
 
+def best_window(bits_or_words, n, window):
+    """cobs_gpu_best_window -> (best, start): the largest number of set positions in any min(window, n) consecutive
+    positions of one hit (its Search.hit_positions words, or a bool vector of at least n positions), and the smallest
+    start that reaches it -- what Search.search_window scores the document with.  Host arithmetic, no device; bits at
+    or beyond n are ignored."""
+    a = np.asarray(bits_or_words)
+    if a.dtype == np.bool_:
+        a = np.packbits(np.concatenate([a, np.zeros(-len(a) % 64, dtype=bool)]), bitorder="little").view("<u8")
+    w = np.ascontiguousarray(a, dtype="<u8")
+    n = int(n)
+    if n < 0 or len(w) * 64 < n:
+        raise ValueError("fewer than n positions given")
+    start = C.c_size_t(0)
+    best = _capi.load().cobs_gpu_best_window(C.cast(w.ctypes.data, C.POINTER(C.c_uint64)), n, int(window), C.byref(start))
+    return int(best), int(start.value)
+
+
 def _as_bytes(q):
     return q.encode("latin-1") if isinstance(q, str) else bytes(q)
 
@@ -949,6 +966,62 @@ class Search:
         """stage times of the coverage searches since the previous call of this method (HIP events, summed over passes)"""
         t = (C.c_double * 3)()
         check(self._lib.cobs_gpu_coverage_ms(self._h, C.byref(t)))
+        return {"hash_ms": t[0], "scan_ms": t[1], "passes": int(t[2])}
+
+    # -- window search: score documents by their best window of the query -------------
+    def search_window_arrays(self, queries, window, threshold=0.0, num_results=0):
+        """cobs_gpu_search_window -> (offsets uint64 [nq + 1], hits HIT_DTYPE): the records of query q are
+        hits[offsets[q]:offsets[q + 1]], by best descending, then (file_no, doc); `score` is the largest number of set
+        positions in any w = min(window, the query's positions) consecutive positions of the query; a document is a hit
+        when it reaches max(1, ceil(threshold * w))."""
+        if type(self)._search_batch_call is not Search._search_batch_call:
+            raise CobsGpuError(_capi.ERR_UNSUPPORTED, "window: not on a device-list handle (the call has no counterpart there)")
+        window = int(window)
+        if not 0 <= window <= 0xFFFFFFFF:
+            raise CobsGpuError(_capi.ERR_ARG, "window: not a 32-bit count of positions")
+        qs = [q if type(q) is bytes else _as_bytes(q) for q in queries]
+        nq = len(qs)
+        arr = (C.c_char_p * max(nq, 1))(*qs)
+        lens = (C.c_size_t * max(nq, 1))(*[len(q) for q in qs])
+        offs = np.zeros(nq + 1, dtype=np.uint64)
+        bad = C.c_size_t(0)
+        if num_results > 0:
+            cap = nq * min(int(num_results), self.total_counts)
+        elif threshold <= 0:
+            cap = nq * self.total_counts
+        else:
+            # (a buffer that proves too small costs a second run of the whole call: sized by the hits per query of the
+            # earlier thresholded window calls on this handle)
+            cap = max(16 * nq, int(self.__dict__.get("_window_hits_per_query", 0.0) * nq * 1.25)) + 1024
+        cap = max(1, cap)
+        while True:
+            hits = np.zeros(cap, dtype=self.HIT_DTYPE)
+            st = self._lib.cobs_gpu_search_window(
+                self._h, arr, lens, nq, window, float(threshold), int(num_results), C.cast(hits.ctypes.data, C.POINTER(Hit)),
+                cap, C.cast(offs.ctypes.data, C.POINTER(C.c_size_t)), C.byref(bad))
+            if st == _capi.ERR_CAPACITY and int(offs[nq]) > cap:
+                cap = int(offs[nq])
+                continue
+            check(st)
+            break
+        if threshold > 0 and num_results == 0 and nq:
+            self._window_hits_per_query = max(int(offs[nq]) / nq, 0.95 * self.__dict__.get("_window_hits_per_query", 0.0))
+        return offs, hits[:int(offs[nq])]
+
+    def search_window(self, query, window, threshold=0.0, num_results=0):
+        """one query -> [SearchResult] in result order (doc_name, best window); a list or tuple of queries -> one such
+        list per query"""
+        many = isinstance(query, (list, tuple))
+        offs, hits = self.search_window_arrays(list(query) if many else [query], window, threshold, num_results)
+        rows = hits.tolist()
+        out = [[SearchResult(self.doc_name(f, d), sc) for (f, d, sc) in rows[int(offs[i]):int(offs[i + 1])]]
+               for i in range(len(offs) - 1)]
+        return out if many else out[0]
+
+    def window_ms(self):
+        """stage times of the window searches since the previous call of this method (HIP events, summed over passes)"""
+        t = (C.c_double * 3)()
+        check(self._lib.cobs_gpu_window_ms(self._h, C.byref(t)))
         return {"hash_ms": t[0], "scan_ms": t[1], "passes": int(t[2])}
 
     # -- document sets: score a query against labelled groups of documents ----------

@@ -355,6 +355,46 @@ cobs_gpu_status cobs_gpu_search_coverage(cobs_gpu_index* ix, const char* const* 
                                          cobs_gpu_hit* hits, size_t cap, size_t* hit_offsets /* nq + 1 */,
                                          size_t* bad_query);
 
+/* ---- window search -------------------------------------------------------- */
+/* A search whose score is LOCAL to the query, beyond the reference: the largest number of set positions in any window of
+ * `window` consecutive positions.  It is the call for a long query (a nanopore read, a contig, a plasmid) searched in
+ * documents that may hold only a short stretch of it: 1 000 consecutive positions of a 20 000-position query score 0.05
+ * in every global search, and 1 000 of 1 000 here with window = 1000.
+ *   File and query.  File f has term size k_f, the handle findere z; query q has n = len(q) - k_f + 1 - z positions in f.
+ *   Set position.    Position p is set in document d exactly as cobs_gpu_prevalence and cobs_gpu_hit_positions define it:
+ *                    terms p .. p + z are all present (the invalid-bases policy included, through K1's table).
+ *   Window.          w = min(window, n).  best(q, f, d) = the maximum over s in [0, n - w] of the number of set positions
+ *                    in [s, s + w): 0 .. w.  best <= min(w, score of the plain search); window >= n gives that score,
+ *                    window = 1 gives 1 where any position is set; best does not decrease when the window grows.
+ *   Threshold.       For threshold > 0 a real document is a hit when best >= max(1, ceil(threshold * w)), computed in
+ *                    double.  For threshold <= 0 every real document is returned, best 0 included.
+ *   Invalid bases.   Under COBS_GPU_INVALID_MISS and _SKIP a position whose characters hold a non-ACGT character is not
+ *                    set; the denominator is w under both, so the two policies give the SAME result here.  Under _ERROR
+ *                    an invalid base fails the call as it does for a search.
+ *   Order.           Per query the records are ordered by best descending, then (file_no, doc) ascending, and cut to the
+ *                    first num_results when num_results > 0; the reference's index-order rule does NOT apply.
+ *                    hits[hit_offsets[q] .. hit_offsets[q+1]) belong to query q, `score` carries best.
+ * Everything the host can refuse is refused before any device work: COBS_GPU_ERR_ARG (NULL arguments, window = 0),
+ * COBS_GPU_ERR_UNSUPPORTED for window > 4095 (the scan's counters have 12 planes), on a handle opened with an HBM budget
+ * (its rows are not all resident) or as one shard of several, COBS_GPU_ERR_QUERY_TOO_SHORT, COBS_GPU_ERR_QUERY_TOO_LONG
+ * for len(q) >= 2^30 (the scan walks 32-bit positions; *bad_query = the offending query).  The device list
+ * (cobs_gpu_multi_*) has no counterpart.  COBS_GPU_ERR_INVALID_BASE comes from the device (*bad_query).
+ * COBS_GPU_ERR_CAPACITY when cap is too small -- hit_offsets then holds the needed sizes (hit_offsets[nq] the total),
+ * known from the one scan that ran (hits may be NULL when cap is 0).  COBS_GPU_ERR_HIP when the device has no room for
+ * the hit records of a pass.
+ * On the device: K1 and one scan that walks every document's positions in order with the window's count kept bit-sliced
+ * (as its distance to the best so far) and appends the documents that pass to a pool; no score matrix exists, and the
+ * counters do not bound the query's length.  cobs_gpu_window_ms (cobs_gpu_diag.h) reads the timers.
+ * cobs_gpu_best_window is the same number on the host, from one cobs_gpu_hit_positions bitmap of n positions (bit p of
+ * words[p / 64]; bits at or beyond n are ignored; n = 0, window = 0 or words = NULL give 0).  *start (may be NULL)
+ * receives the smallest s whose window reaches it -- the device call does not report it.  For every hit of any search,
+ *   cobs_gpu_best_window(its bitmap, n, window, NULL) == the best cobs_gpu_search_window gives the document. */
+uint32_t cobs_gpu_best_window(const uint64_t* words, size_t n, uint32_t window, size_t* start);   /* host arithmetic, no device */
+cobs_gpu_status cobs_gpu_search_window(cobs_gpu_index* ix, const char* const* queries, const size_t* lens, size_t nq,
+                                       uint32_t window, double threshold, size_t num_results,
+                                       cobs_gpu_hit* hits, size_t cap, size_t* hit_offsets /* nq + 1 */,
+                                       size_t* bad_query);
+
 /* score slots per query held by THIS shard (== cobs_gpu_total_counts when
  * unsharded); device count rows have this many elements */
 uint64_t cobs_gpu_local_counts(const cobs_gpu_index* ix);

@@ -104,6 +104,10 @@ cobs_gpu_status cobs_gpu_set_quorum_ms(cobs_gpu_index* ix, double out[5]);   /* 
  * overflow included), out[2] = passes. */
 cobs_gpu_status cobs_gpu_coverage_ms(cobs_gpu_index* ix, double out[3]);   /* hash, scan, passes; reset on read */
 
+/* The same for the cobs_gpu_search_window calls on this handle: out[0] = K1 (hashing), out[1] = the window scan (a scan
+ * repeated after a pool overflow included), out[2] = passes. */
+cobs_gpu_status cobs_gpu_window_ms(cobs_gpu_index* ix, double out[3]);     /* hash, scan, passes; reset on read */
+
 /* Durations (ms) of the LAST cobs_gpu_search_groups call on this handle: out[0] = the accumulate kernel (HIP events, summed
  * over the call's passes), out[1] = the select kernel (HIP events), out[2] = the host's ordering of the records. */
 cobs_gpu_status cobs_gpu_groups_ms(cobs_gpu_index* ix, double out[3]);

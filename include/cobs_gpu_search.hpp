@@ -60,6 +60,14 @@ inline uint64_t covered_bases(const std::vector<uint64_t>& words, size_t n, uint
     return cobs_gpu_covered_bases(words.data(), n, span);
 }
 
+//! The largest number of set positions in any min(window, n) consecutive positions of one cobs_gpu_hit_positions bitmap
+//! of n positions, and (start, optional) the smallest start that reaches it: what ClassicSearch::search_window scores
+//! the document with.  Host arithmetic (cobs_gpu_best_window); Error(COBS_GPU_ERR_ARG) when words is too short for n.
+inline uint32_t best_window(const std::vector<uint64_t>& words, size_t n, uint32_t window, size_t* start = nullptr) {
+    if (n > words.size() * 64) throw Error(COBS_GPU_ERR_ARG, "best_window: words holds fewer than n positions");
+    return cobs_gpu_best_window(words.data(), n, window, start);
+}
+
 //! The reference's Search carries a public `Timer timer_` with an accessor `timer()` (cobs/query/search.hpp:35-46,
 //! cobs/util/timer.hpp:19-55) that its callers read and reset: `s.timer().print("search")` (src/cobs.cpp:468),
 //! `s.timer().reset()` and `cobs::Timer t = s.timer(); t.get("hashes") ...` in benchmark_fpr_run (:623, :644-661).
@@ -502,6 +510,59 @@ public:
         for (size_t q = 0; q < nq; ++q)
             for (size_t i = offs[q]; i < offs[q + 1]; ++i)
                 results[q].push_back(SearchResult(cobs_gpu_doc_name(ix_, hits[i].file_no, hits[i].doc), hits[i].score));
+    }
+
+    //! Window search (beyond the reference; cobs_gpu_search_window): a document scores the largest number of set positions
+    //! in any w = min(window, the query's positions) consecutive positions of the query and is a hit when that reaches
+    //! max(1, ceil(threshold * w)); results[q] is ordered by that number descending, then (file, document), and
+    //! SearchResult::score carries it.  window: 1 .. 4095.  positions (optional) receives the cobs_gpu_hit_positions words
+    //! of every result and num_positions its n, parallel to results[q]: best_window over them gives the window's start.
+    void search_window(const std::vector<std::string>& queries, uint32_t window, std::vector<std::vector<SearchResult>>& results,
+                       double threshold = 0.0, size_t num_results = 0,
+                       std::vector<std::vector<std::vector<uint64_t>>>* positions = nullptr,
+                       std::vector<std::vector<size_t>>* num_positions = nullptr) {
+        std::vector<const char*> qp;
+        std::vector<size_t> ql;
+        for (const auto& q : queries) { qp.push_back(q.data()); ql.push_back(q.size()); }
+        const size_t nq = queries.size();
+        std::vector<size_t> offs(nq + 1, 0);
+        std::vector<cobs_gpu_hit> hits(16 * nq + 1024);
+        size_t bad = 0;
+        cobs_gpu_status st;
+        for (;;) {
+            st = cobs_gpu_search_window(ix_, qp.data(), ql.data(), nq, window, threshold, num_results, hits.data(), hits.size(),
+                                        offs.data(), &bad);
+            if (st != COBS_GPU_ERR_CAPACITY || offs[nq] <= hits.size()) break;
+            hits.resize(offs[nq]);          // (the call reported the needed size)
+        }
+        check(st);
+        results.assign(nq, {});
+        for (size_t q = 0; q < nq; ++q)
+            for (size_t i = offs[q]; i < offs[q + 1]; ++i)
+                results[q].push_back(SearchResult(cobs_gpu_doc_name(ix_, hits[i].file_no, hits[i].doc), hits[i].score));
+        if (!positions) return;
+        std::vector<size_t> bo(offs[nq] + 1, 0);
+        std::vector<uint64_t> bits;
+        size_t need = 0;
+        st = cobs_gpu_hit_positions(ix_, qp.data(), ql.data(), nq, hits.data(), offs.data(), nullptr, 0, bo.data(), &need, &bad);
+        if (st == COBS_GPU_ERR_CAPACITY && need > 0) {       // the size is host arithmetic: nothing has run yet
+            bits.resize(need);
+            st = cobs_gpu_hit_positions(ix_, qp.data(), ql.data(), nq, hits.data(), offs.data(), bits.data(), bits.size(), bo.data(),
+                                        &need, &bad);
+        }
+        check(st);
+        const size_t z = findere();
+        positions->assign(nq, {});
+        if (num_positions) num_positions->assign(nq, {});
+        for (size_t q = 0; q < nq; ++q)
+            for (size_t i = offs[q]; i < offs[q + 1]; ++i) {
+                (*positions)[q].emplace_back(bits.begin() + bo[i], bits.begin() + bo[i + 1]);
+                if (num_positions) {
+                    cobs_gpu_index_info info;
+                    check(cobs_gpu_info(ix_, hits[i].file_no, &info));
+                    (*num_positions)[q].push_back(ql[q] - info.term_size + 1 - z);
+                }
+            }
     }
 
     //! one document of a group's result: the sum of the scores of the group's queries and how many of them it was a hit of

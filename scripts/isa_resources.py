@@ -16,7 +16,8 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KERNEL_FILES = ("hash_kernels", "kernels", "scan_findere", "topk_kernels", "build_kernels", "group_kernels", "fill_kernels",
-                "prevalence_kernels", "weighted_kernels", "set_kernels", "set_count_kernels", "coverage_kernels", "presence_kernels", "fetch_kernels")
+                "prevalence_kernels", "weighted_kernels", "set_kernels", "set_count_kernels", "coverage_kernels", "window_kernels", "presence_kernels",
+                "fetch_kernels")
 
 
 def main():
@@ -27,7 +28,8 @@ def main():
     # kernels (group_kernels.hip: accumulate, select, zero) and the filter-fill
     # kernels (fill_kernels.hip: count, its load-only probe, zero), the prevalence kernels (prevalence_kernels.hip), the
     # kernels of the weighted search (weighted_kernels.hip: weights, weighted scan), the document-set kernels
-    # (set_kernels.hip: set presence, select; set_count_kernels.hip: set count, quorum select), the coverage scan (coverage_kernels.hip), and the other readers of K1's
+    # (set_kernels.hip: set presence, select; set_count_kernels.hip: set count, quorum select), the coverage scan (coverage_kernels.hip), the window scan
+    # (window_kernels.hip), and the other readers of K1's
     # row-index table (row_table.hpp): the presence kernel and the out-of-core fetch kernels
     asm = ""
     for name in KERNEL_FILES:
