@@ -27,15 +27,16 @@ from tests import prevalence_check as V
 from tests import set_quorum_check as Q
 from tests import sets_check as S
 from tests import weighted_check as W
+from tests import window_check as B
 
 FAMILIES = ("search_small", "search_large", "counts", "view", "positions", "prevalence", "weighted", "coverage", "sets",
-            "quorum", "set_prevalence", "groups", "doc_bits", "own_batch")
+            "quorum", "set_prevalence", "groups", "doc_bits", "own_batch", "window", "window_positions", "adjusted")
 SET_FAMILIES = ("sets", "quorum", "set_prevalence")
 KINDS = ("invalid_base", "too_short", "overflow")              # the failure steps
 CAN_FAIL = {
     "invalid_base": tuple(f for f in FAMILIES if f != "doc_bits"),
     "too_short": tuple(f for f in FAMILIES if f != "doc_bits"),
-    "overflow": ("search_small", "search_large", "view", "groups", "sets", "coverage", "weighted"),
+    "overflow": ("search_small", "search_large", "view", "groups", "sets", "coverage", "weighted", "window"),
 }
 K_MAX = 31                                                     # the largest term size of the handles the plan is walked on
 ZS = (0, 3)
@@ -45,6 +46,8 @@ PASS_BYTES = (0, PASS_SMALL)
 GRAPHS = (-1, 0)                                               # automatic | off
 SEARCHES = ((0.0, 0), (0.5, 0), (0.0, 3), (0.5, 3))
 QUORUMS = (0.5, 0.95, 1.0)
+WINDOWS = (7, 64, 300, 4095)                                   # one per plane count of the window scan (6, 8, 10, 12)
+WINDOW_FAMILIES = ("window", "window_positions")
 NQS = (1, 2, 16, 17, 24)
 NQS_SMALL = (1, 2, 16)
 LABEL_STATES = ("initial", "relabel1", "relabel2", "cleared", "again")
@@ -86,6 +89,16 @@ def _setting_rows():
     for r in range(14):
         rows.append((ZS[r % 2], POLICIES[(r // 2) % 3], PASS_BYTES[1 if 6 <= r < 12 else 0], GRAPHS[1 if r in (3, 8, 12, 13) else 0]))
     return rows
+
+
+# the window of a window step follows its setting row: every W meets both z, both pass_bytes and all three policies in the
+# family's first 14 regular steps, whatever the seed (W 7: the rows 0, 3, 10, 13; 64: 1, 5, 8; 300: 4, 6, 9; 4095: 2, 7, 11, 12)
+_WINDOW_OF_ROW = (0, 1, 3, 0, 2, 1, 2, 3, 1, 2, 0, 3, 3, 0)
+
+
+def _window(row, j):
+    """the W of the j-th step of a window family under setting row `row`; the second turn through the rows shifts it"""
+    return WINDOWS[(_WINDOW_OF_ROW[row] + 2 * (j // len(_WINDOW_OF_ROW))) % len(WINDOWS)]
 
 
 # ---- the labels -----------------------------------------------------------------------------------------------------------
@@ -236,10 +249,10 @@ def _choose_failing_families(seq, states):
 
 def _query_count(fam, kind, j, many):
     """search_large always sends 24 queries -- above the 16 of a captured graph: the pipelined passes --, its failure
-    steps included; the overflow step of every other family sends 16"""
+    steps included; counts and adjusted take one query; the overflow step of every other family sends 16"""
     if fam == "search_large":
         return 24
-    if fam == "counts":
+    if fam in ("counts", "adjusted"):
         return 1
     if kind == "overflow":
         return 16
@@ -253,6 +266,8 @@ def _step_queries(rng, fam, kind, j, z, policy, many, params):
     nq = _query_count(fam, kind, j, many)
     has_long = bool(many or rng.integers(2))
     with_n = policy != "error" and bool(rng.integers(3))
+    if fam == "adjusted" and policy == "skip":
+        with_n = True                                                   # P is the count of the valid positions, not T - z
     if kind == "overflow":
         has_long, with_n = False, False
     queries = list(make_batch(rng, nq, z, has_long, with_n, many=many and nq == 24))
@@ -267,12 +282,16 @@ def _step_queries(rng, fam, kind, j, z, policy, many, params):
     return tuple(queries)
 
 
-def _family_params(fam, kind, i, j, nq, params):
-    """what the family's call takes besides the queries (own_batch: see _own_batch_step)"""
+def _family_params(fam, kind, i, j, nq, row, params):
+    """what the family's call takes besides the queries (own_batch: see _own_batch_step); row: the step's setting row"""
     overflow = kind == "overflow"
     t, lim = (OVERFLOW_T, 0) if overflow else SEARCHES[(j + i) % 4]
-    if fam in ("search_small", "search_large", "view", "weighted", "coverage"):
+    if fam in ("search_small", "search_large", "view", "weighted", "coverage", "adjusted"):
         params.update(t=t, lim=lim)
+    elif fam == "window":
+        params.update(W=_window(row, j), t=t, lim=lim)
+    elif fam == "window_positions":
+        params.update(W=_window(row, j))
     elif fam == "sets":
         params.update(t=0.0 if overflow else (0.0, 0.3)[j % 2], rank_by=("any", "all")[(j // 2) % 2],
                       lim=0 if overflow else (0, 2)[(j // 4) % 2])
@@ -309,12 +328,13 @@ def build_plan(seed=None):
     _choose_failing_families(seq, states)
     # the settings: per family a seeded permutation of the 14 rows, taken by the family's regular occurrences in turn
     rows = _setting_rows()
-    perm = {f: [rows[int(j)] for j in rng.permutation(len(rows))] for f in FAMILIES}
+    perm = {f: [int(j) for j in rng.permutation(len(rows))] for f in FAMILIES}
     count = collections.Counter()
     steps, own, prev = [], None, None
     for i, (fam, kind, after) in enumerate(seq):
         j = count[fam]
-        z, policy, pass_bytes, graph = perm[fam][j % len(rows)]
+        row = perm[fam][j % len(rows)]
+        z, policy, pass_bytes, graph = rows[row]
         if kind == "regular":
             count[fam] += 1
         else:
@@ -323,7 +343,7 @@ def build_plan(seed=None):
                 policy = "error"
         params = {}
         queries = _step_queries(rng, fam, kind, j, z, policy, pass_bytes != 0, params)
-        _family_params(fam, kind, i, j, len(queries), params)
+        _family_params(fam, kind, i, j, len(queries), row, params)
         if fam == "own_batch":
             own, queries = _own_batch_step(own, kind, j, queries, z, policy, params)
         steps.append(Step(i, fam, prev, kind, after, z, policy, states[i], pass_bytes, graph, queries, params))
@@ -334,16 +354,18 @@ def build_plan(seed=None):
 # ---- the device passes ----------------------------------------------------------------------------------------------------
 
 PASS_READERS = {"positions": "positions_ms", "prevalence": "prevalence_ms", "weighted": "weighted_ms", "coverage": "coverage_ms",
-                "sets": "sets_ms", "quorum": "set_quorum_ms", "set_prevalence": "set_quorum_ms"}
+                "sets": "sets_ms", "quorum": "set_quorum_ms", "set_prevalence": "set_quorum_ms", "window": "window_ms",
+                "window_positions": "positions_ms"}
 
 
 def needs_three_passes(st, expect):
     """must the step's call take at least 3 device passes (read off the family's *_ms reader)?  The small pass_bytes with
     the 24-query batch (make_batch: more than 2 * PASS_SMALL bytes of K1's table); hit_positions only looks up the queries
-    that have a hit, and a set search without a labelled file has no work item"""
+    that have a hit (window_positions: a window hit), and a set search without a labelled file has no work item; a
+    window search at threshold 0 adds its pool's bytes to the estimate: more passes, never fewer"""
     if st.kind != "regular" or st.family not in PASS_READERS or not st.pass_bytes or len(st.queries) != 24:
         return False
-    if st.family == "positions":
+    if st.family in ("positions", "window_positions"):
         return all(len(hits) > 0 for hits in expect.value(st)[0])
     if st.family in SET_FAMILIES:
         return any(lab is not None for lab in expect.labels(st.labels))
@@ -363,6 +385,7 @@ class Expect:
     def __init__(self, files):
         self.files = list(files)
         self._cache = {}
+        self._packed = {}                                               # file -> the packed positions of the last query asked about
         self._labels = {s: labelings(s, self.files) for s in LABEL_STATES}
 
     def labels(self, state):
@@ -384,8 +407,53 @@ class Expect:
         fn = F.counts if policy == "error" else I.counts
         return self._memo(("counts", q, z, policy), lambda: [int(x) for x in fn(self.files, q, z)])
 
+    def slot_of(self, f):
+        """{document: score slot} of file f (FileBits.doc_of_slot, inverted; padding slots have no document)"""
+        return self._memo(("slot_of", f), lambda: {int(doc): s for s, doc in enumerate(self.files[f].doc_of_slot()) if doc >= 0})
+
     def position_words(self, q, z, policy, f, d):
-        return [int(x) for x in P.pack(P.positions(self.files, q, z, f, d, policy))]
+        """positions_check.pack(positions_check.positions(files, q, z, f, d, policy)) as a list of ints.  The hits of a
+        query come one after the other, so the columns of all slots of (query, file) are packed at once and kept until
+        the next query (tests/test_call_sequence_cpu.py holds this against the checker's own two calls)"""
+        key = (q, z, policy)
+        if self._packed.get(f, (None,))[0] != key:
+            fb = self.files[f]
+            cols = V.windows(fb, q, z, policy)                          # bool [n, slots]: what positions() takes its column from
+            win = np.zeros((fb.slots, (cols.shape[0] + 63) // 64 * 64), dtype=np.uint8)
+            win[:, :cols.shape[0]] = cols.T
+            words = np.packbits(win, axis=1, bitorder="little").view("<u8")         # [slots, words]; bits >= n zero
+            self._packed[f] = (key, words)
+        return self._packed[f][1][self.slot_of(f)[d]].tolist()
+
+    def window_tables(self, q, z, W, policy):
+        """window_check.tables of one query: per file (w, best of every slot, document of every slot, plain scores)"""
+        return self._memo(("window", q, z, W, policy), lambda: B.tables(self.files, q, z, W, policy))
+
+    def window(self, queries, z, policy, W, t, lim):
+        return [B.results_from(self.window_tables(q, z, W, policy), t, lim) for q in queries]
+
+    def valid_positions(self, q, z, policy, f):
+        """the positions of q that a search of file f scores: T - z, under `skip` those whose k + z characters hold no N"""
+        span = self.files[f].term_size + z
+        n = len(q) - span + 1
+        if policy != "skip":
+            return n
+        return sum(1 for p in range(n) if all(c in b"ACGT" for c in q[p:p + span]))
+
+    def adjusted_floats(self, st):
+        """[(expected_fp, adjusted)] of the results of an `adjusted` step, in result order: fill_check.adjust over the
+        document's set bits and the signature size of its sub-index (compared with a tolerance, apart from value())"""
+        q, z, pol = st.queries[0], st.z, st.policy
+        out = []
+        for (f, d, score) in self.search((q,), z, pol, st.params["t"], st.params["lim"])[0]:
+            fb = self.files[f]
+            bits = self._memo(("bits", f), lambda: FC.bits_of_mats(fb.mats))
+            sigs = self._memo(("sigs", f), lambda: np.repeat([m.shape[0] for m in fb.mats], [m.shape[1] * 8 for m in fb.mats]))
+            P = self._memo(("valid", q, z, pol, f), lambda: self.valid_positions(q, z, pol, f))
+            slot = self.slot_of(f)[d]                                   # (bits and sigs are in slot order)
+            a = FC.adjust(score, P, int(bits[slot]), int(sigs[slot]), fb.num_hashes, z)
+            out.append((a["expected_fp"], a["adjusted"]))
+        return out
 
     def value(self, st):
         """the expected value of a regular (or overflow) step"""
@@ -411,6 +479,13 @@ class Expect:
             return ([W.results_from(tab, p["t"], p["lim"]) for tab in tabs], [[int(t[0]) for t in tab] for tab in tabs])
         if fam == "coverage":
             return [G.results(files, q, z, p["t"], p["lim"], pol) for q in qs]
+        if fam == "window":
+            return self.window(qs, z, pol, p["W"], p["t"], p["lim"])
+        if fam == "window_positions":
+            hits = self.window(qs, z, pol, p["W"], 0.5, 0)
+            return (hits, [[self.position_words(q, z, pol, f, d) for (f, d, _sc) in hs] for q, hs in zip(qs, hits)])
+        if fam == "adjusted":                                           # (document, score); the floats: adjusted_floats
+            return [(d, sc) for (_f, d, sc) in self.search(qs, z, pol, p["t"], p["lim"])[0]]
         labs = self.labels(st.labels)
         if fam == "sets":
             offs, rows = S.arrays(files, labs, list(qs), z, p["t"], p["rank_by"], p["lim"], pol)
@@ -442,7 +517,7 @@ class Expect:
         v = self.value(st)
         if st.family in ("prevalence", "set_prevalence"):
             return any_in(v[1])
-        if st.family in ("weighted", "groups", "positions"):
+        if st.family in ("weighted", "groups", "positions", "window_positions"):
             return any_in(v[0])
         return any_in(v)
 

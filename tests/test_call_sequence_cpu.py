@@ -10,6 +10,8 @@ import pytest
 
 from tests import call_sequence as CS
 from tests import invalid_check as I
+from tests import positions_check as PC
+from tests.test_gpu_window import _partial
 
 
 @pytest.fixture(scope="module")
@@ -27,14 +29,14 @@ def handles(tmp_path_factory):
 
 
 def test_every_ordered_pair_of_families(plan):
-    assert len(CS.FAMILIES) == 14 and len(set(CS.FAMILIES)) == 14
+    assert len(CS.FAMILIES) == 17 and len(set(CS.FAMILIES)) == 17
     pairs = {(a.family, b.family) for a, b in zip(plan, plan[1:])}
     assert pairs == set(itertools.product(CS.FAMILIES, CS.FAMILIES))
     # ... and between two REGULAR steps too (the failure steps were put behind an occurrence of their follower's family)
     regular = {(a.family, b.family) for a, b in zip(plan, plan[1:]) if a.kind == "regular" and b.kind == "regular"}
     assert regular == set(itertools.product(CS.FAMILIES, CS.FAMILIES))
     assert all(st.index == i and st.prev == (plan[i - 1].family if i else None) for i, st in enumerate(plan))
-    assert len(plan) == 14 * 14 + 1 + 2 * 3 * 14
+    assert len(plan) == 17 * 17 + 1 + 2 * 3 * 17
 
 
 def test_every_family_meets_every_setting(plan):
@@ -47,6 +49,14 @@ def test_every_family_meets_every_setting(plan):
         assert {st.graph for st in mine} == set(CS.GRAPHS), fam
     for fam in CS.SET_FAMILIES:
         assert {st.labels for st in regular if st.family == fam} == set(CS.LABEL_STATES), fam
+    # every window (one per plane count of the scan) meets both z, both pass_bytes and all three policies
+    for fam in CS.WINDOW_FAMILIES:
+        assert {st.params["W"] for st in plan if st.family == fam} == set(CS.WINDOWS), fam
+        for W in CS.WINDOWS:
+            mine = [st for st in regular if st.family == fam and st.params["W"] == W]
+            assert {st.z for st in mine} == set(CS.ZS), (fam, W)
+            assert {st.policy for st in mine} == set(CS.POLICIES), (fam, W)
+            assert {st.pass_bytes for st in mine} == set(CS.PASS_BYTES), (fam, W)
     # the label states come in time order
     order = [k for k, _g in itertools.groupby(st.labels for st in plan)]
     assert order == list(CS.LABEL_STATES)
@@ -57,15 +67,15 @@ def test_every_family_meets_every_setting(plan):
     large = [st for st in plan if st.family == "search_large"]
     assert {len(st.queries) for st in large} == {24} and {st.kind for st in large} == {"regular"} | set(CS.KINDS)
     assert all(len(st.queries) == 16 for st in plan if st.kind == "overflow" and st.family != "search_large")
-    feature = [st for st in regular if st.family not in ("search_small", "search_large", "counts", "doc_bits", "own_batch")]
+    feature = [st for st in regular if st.family not in ("search_small", "search_large", "counts", "doc_bits", "own_batch", "adjusted")]
     assert {len(st.queries) for st in feature} == set(CS.NQS)
     widths = [max(len(q) for q in st.queries) - CS.K_MAX + 1 - st.z > 255 for st in regular]
     assert sum(a != b for a, b in zip(widths, widths[1:])) > 40
     assert all(len(q) - CS.K_MAX + 1 - st.z <= 700 for st in plan for q in st.queries)          # no 32-bit query
-    for st in regular:
+    fresh = [st for st in regular if st.params.get("what") != "reread"]              # (a second reading keeps its run's queries
+    for st in fresh:                                                                 # and sends nothing to the device)
         if st.pass_bytes and len(st.queries) == 24:
             assert sum(len(q) + 16 for q in st.queries) * 16 > 2 * CS.PASS_SMALL, CS.describe(st)
-    fresh = [st for st in regular if st.params.get("what") != "reread"]              # (a second reading keeps its run's queries)
     assert all(len(q) >= CS.K_MAX + st.z for st in fresh for q in st.queries)
     assert sum(len(st.queries[0]) == CS.K_MAX + st.z for st in fresh) > 50          # the shortest query there is
 
@@ -126,6 +136,8 @@ def test_the_expectations_are_not_vacuous(plan, handles, name):
     t0 = time.perf_counter()
     nonempty = {fam: 0 for fam in CS.FAMILIES}
     some_not_all = any_ne_all = partial_cover = n_matters = overflows = 0
+    win_partial = win_some_not_all = win_n_matters = w_differs = adjusted_between = adjusted_skip_n = words_anchored = 0
+    whole_steps = set()
     for st in plan:
         if st.kind in ("invalid_base", "too_short"):
             continue
@@ -148,8 +160,45 @@ def test_the_expectations_are_not_vacuous(plan, handles, name):
                 if b"N" in q:
                     clean = q.replace(b"N", b"A")
                     n_matters += ex.search((clean,), st.z, st.policy, st.params["t"], st.params["lim"])[0] != v[i]
+        if st.family == "window":
+            W, t, lim = st.params["W"], st.params["t"], st.params["lim"]
+            tabs = [ex.window_tables(q, st.z, W, st.policy) for q in st.queries]
+            win_partial += _partial(tabs)                               # not the plain search's answer
+            if t > 0 and lim == 0:
+                every = ex.window(st.queries, st.z, st.policy, W, 0.0, 0)
+                win_some_not_all += any(0 < len(got) < len(full) for got, full in zip(v, every))
+            if st.policy != "error":
+                for i, q in enumerate(st.queries):
+                    if b"N" in q:
+                        win_n_matters += ex.window((q.replace(b"N", b"A"),), st.z, st.policy, W, t, lim)[0] != v[i]
+            if W == max(CS.WINDOWS) and len(files) > 1:                 # w = n, and n differs between the files
+                assert all(tab[f][0] == fb.positions(q, st.z) for q, tab in zip(st.queries, tabs) for f, fb in enumerate(files))
+                w_differs += any(len({w for (w, _b, _docs, _sc) in tab}) > 1 for tab in tabs)
+        if st.family in ("positions", "window_positions"):
+            # Expect.position_words packs all documents of a query at once: against the checker's own two calls, EVERY hit
+            # of the first step of each (family, policy, z), some hits of every query of the others
+            whole = (st.family, st.policy, st.z) not in whole_steps
+            whole_steps.add((st.family, st.policy, st.z))
+            for q, hs, ws in zip(st.queries, v[0], v[1]):
+                assert len(hs) == len(ws)
+                for (f, d, _sc), words in list(zip(hs, ws))[::1 if whole else max(1, len(hs) // 3)]:
+                    assert words == [int(x) for x in PC.pack(PC.positions(files, q, st.z, f, d, st.policy))], CS.describe(st)
+                    words_anchored += 1
+        if st.family == "window_positions" and st.kind == "regular" and st.pass_bytes and len(st.queries) == 24:
+            # every candidate of the pass guard has a window hit for every query: none drops out of the pass check
+            assert all(len(hits) > 0 for hits in v[0]) and CS.needs_three_passes(st, ex), CS.describe(st)
+        if st.family == "adjusted":
+            q = st.queries[0]
+            floats = ex.adjusted_floats(st)
+            assert len(floats) == len(v)
+            adjusted_between += any(0.0 < a < sc for (_d, sc), (_e, a) in zip(v, floats))
+            if st.policy == "skip" and b"N" in q and len(v) > 0:        # (a step that compares floats)
+                adjusted_skip_n += all(0 < ex.valid_positions(q, st.z, "skip", f) < fb.positions(q, st.z) for f, fb in enumerate(files))
     assert all(nonempty.values()), nonempty
-    assert some_not_all > 0 and any_ne_all > 0 and partial_cover > 0 and n_matters > 0 and overflows == 14
+    assert win_partial > 0 and win_some_not_all > 0 and win_n_matters > 0 and (w_differs > 0 or len(files) == 1)
+    assert adjusted_between > 0 and adjusted_skip_n > 0 and words_anchored > 500
+    assert whole_steps == {(fam, pol, z) for fam in ("positions", "window_positions") for pol in CS.POLICIES for z in CS.ZS}
+    assert some_not_all > 0 and any_ne_all > 0 and partial_cover > 0 and n_matters > 0 and overflows == len(CS.FAMILIES) == 17
     # a step without labels expects what the library documents: every query's list is empty (and the call succeeds)
     for st in plan:
         if st.family in CS.SET_FAMILIES and st.labels == "cleared" and st.kind == "regular":

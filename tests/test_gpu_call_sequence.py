@@ -1,10 +1,11 @@
 """GPU: every call family after every other on ONE handle (the plan of tests/call_sequence.py).  The host-buffer search, counts,
-the view call, hit positions, prevalence, the weighted, coverage, set, quorum and grouped searches, set prevalence and
-doc_bits all work on the handle's scratch workspace; a long-lived Batch of the caller's lives beside it.  One Search and one
-Batch walk the whole plan -- every ordered pair of families, a failing call of every kind in front of every family, findere
-z, the invalid-bases policy, the labels, pass_bytes, graph, the query count and the score width changing between the steps
--- and after EVERY step the answer is compared exactly with the checkers.  A failing step names the pair: the previous
-family, this family and the settings in force."""
+the view call, hit positions, prevalence, the weighted, coverage, set, quorum and grouped searches, set prevalence,
+doc_bits, the window search (at one W per plane count of its scan), hit positions over window hits and the adjusted search
+(which under `skip` opens a short-lived Batch of its own) all work on the handle's scratch workspace; a long-lived Batch of
+the caller's lives beside it.  One Search and one Batch walk the whole plan -- every ordered pair of families, a failing
+call of every kind in front of every family, findere z, the invalid-bases policy, the labels, pass_bytes, graph, the query
+count and the score width changing between the steps -- and after EVERY step the answer is compared exactly with the
+checkers.  A failing step names the pair: the previous family, this family and the settings in force."""
 import gc
 import time
 
@@ -38,6 +39,7 @@ class Walker:
     def __init__(self, lib, search, batch, expect):
         self.lib, self.s, self.b, self.ex = lib, search, batch, expect
         self.z, self.policy, self.labels, self.pass_bytes, self.graph = 0, "error", None, 0, -1
+        self.floats = None                                              # (expected_fp, adjusted) of the last search_adjusted
 
     def settle(self, st):
         """bring the handle to the step's settings (only what differs is set: the calls in between see the changes)"""
@@ -92,6 +94,21 @@ class Walker:
             return (_lists(offs, hits), pos.tolist())
         if fam == "doc_bits":
             return [s.doc_bits(f).tolist() for f in range(s.num_files)]
+        if fam == "window":
+            return _lists(*s.search_window_arrays(qs, p["W"], p["t"], p["lim"]))
+        if fam == "window_positions":
+            offs, hits = s.search_window_arrays(qs, p["W"], 0.5, 0)
+            bo, bits = s.hit_positions(qs, offs, hits)                  # (the hits of a window search are a legal input)
+            self.window_identities(st, offs, hits, bo, bits)
+            words = [bits[int(bo[h]):int(bo[h + 1])].tolist() for h in range(len(hits))]
+            return (_lists(offs, hits), [words[int(offs[i]):int(offs[i + 1])] for i in range(len(qs))])
+        if fam == "adjusted":
+            # (under `skip` the call opens a Batch of its own on the handle, beside the walker's and the scratch batch)
+            res = s.search_adjusted(qs[0], p["t"], p["lim"])
+            self.floats = [(r.expected_fp, r.adjusted) for r in res]
+            docs = [int(r.doc_name[4:]) for r in res]
+            assert [r.doc_name for r in res] == ["doc_%05d" % d for d in docs], "%s\n  names %r" % (CS.describe(st), [r.doc_name for r in res][:4])
+            return [(d, r.score) for d, r in zip(docs, res)]
         assert fam == "own_batch"
         b = self.b
         what = p["what"]
@@ -107,11 +124,35 @@ class Walker:
             return [b.hits_host(i, p["k"]) for i in range(len(qs))]
         return [b.counts_host(i).tolist() for i in range(len(qs))]
 
+    def window_identities(self, st, offs, hits, bo, bits):
+        """for every window hit: best_window over its hit_positions words is its score; with W >= n the popcount is"""
+        W = st.params["W"]
+        ks = [fb.term_size for fb in self.ex.files]
+        if not len(hits):
+            return
+        assert bits.dtype == np.uint64 and int(bo[len(hits)]) == len(bits), CS.describe(st)
+        ones = np.unpackbits(bits.view(np.uint8)).reshape(-1, 64).sum(axis=1)       # the set bits of every word
+        pops = np.add.reduceat(ones, bo[:-1].astype(np.int64)).tolist()             # ... of every hit (none has no word)
+        files, scores, bo = hits["file_no"].tolist(), hits["score"].tolist(), bo.tolist()
+        for i, q in enumerate(st.queries):
+            for h in range(int(offs[i]), int(offs[i + 1])):
+                n = len(q) - ks[files[h]] + 1 - st.z
+                best = self.lib.best_window(bits[bo[h]:bo[h + 1]], n, W)[0]
+                assert best == scores[h], "%s\n  query %d, hit %d: best_window %d, score %d" % (CS.describe(st), i, h, best, scores[h])
+                if W >= n:
+                    assert pops[h] == scores[h], "%s\n  query %d, hit %d: popcount %d, score %d" % (CS.describe(st), i, h, pops[h], scores[h])
+
     def check(self, st, got, what=""):
         want = self.ex.value(st)
         got = _plain(got)
         if got != _plain(want):
             raise AssertionError("%s%s\n  %s" % (CS.describe(st), what, _first_difference(got, _plain(want))))
+        if st.family == "adjusted":                                     # the floats: to the relative 1e-12 of tests/test_gpu_fill.py
+            want = self.ex.adjusted_floats(st)
+            assert len(self.floats) == len(want), CS.describe(st)
+            for r, (got_f, want_f) in enumerate(zip(self.floats, want)):
+                for name, a, b in zip(("expected_fp", "adjusted"), got_f, want_f):
+                    assert abs(a - b) <= 1e-12 * abs(b), "%s\n  result %d: %s %r, expected %r" % (CS.describe(st), r, name, a, b)
 
     def step(self, st):
         from cobs_amd import _capi
@@ -181,6 +222,8 @@ def test_every_family_after_every_other_on_one_handle(gpu_lib, monkeypatch, tmp_
     for st in plan:                                                     # the expected values first: the walk's time is the library's
         if st.kind in ("regular", "overflow"):
             ex.value(st)
+            if st.family == "adjusted":
+                ex.adjusted_floats(st)
     if handle.endswith("idx64"):
         monkeypatch.setenv("COBS_GPU_IDX64", "1")       # (read when a handle is opened)
 
