@@ -99,7 +99,23 @@ struct ScanArgs {
     // tuning builds (COBS_SCAN_TIMING) only: s_memtime stamps [slot][wave 0..3][8] of every dbg_every-th work-group
     uint64_t* dbg;
     uint32_t dbg_every, dbg_slots;
+    // self_hash != 0 (kernels.hip: SH; term size 31, one hash function, 32-bit indices): no table from K1 -- every
+    // work-group hashes its query's terms for the sub-indexes of its tile into LDS, from the text K1 would have read.
+    // (Appended behind the older members: the kernels that do not read them keep their argument offsets.)
+    const uint8_t* text;        // query characters, query q at text[span_off[q] ..]
+    const uint64_t* span_off;   // nq + 1
+    const uint32_t* q_len;      // characters per query
+    uint32_t* err_query;        // K1's flag word (HashArgs::err_query)
+    uint32_t* valid;            // K1's valid positions per query of this file (HashArgs::valid), or nullptr
+    uint32_t self_hash;
+    uint32_t canonicalize;
+    uint32_t invalid_bases;     // as HashArgs::invalid_bases
+    uint32_t record;            // this launch's tile 0 reports invalid bases / valid positions, once per query as K1 does
 };
+
+// Row indices the self-hashing scan keeps in LDS: (sub-indexes of a tile) x (blocks of the query + a padding block) x 8
+// may not exceed this -- 2048 terms of one sub-index and the padding blocks.
+constexpr uint32_t kSelfHashEntries = 2048u + 64u;
 
 // Owner-routed hit exchange (xchg_kernels.hip): bucket the hit pool by the rank that owns each record's query.
 struct BucketArgs {

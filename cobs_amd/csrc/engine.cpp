@@ -70,6 +70,7 @@ Tuning Tuning::from_env() {
     if (getenv("COBS_GPU_NO_PIN")) t.no_pin = true;
     if (const char* e = getenv("COBS_GPU_GRAPH")) t.graph = atoi(e) != 0;
     if (const char* e = getenv("COBS_GPU_LDS_STAGED")) t.lds_staged = atoi(e) != 0;
+    if (const char* e = getenv("COBS_GPU_SCAN_SELF_HASH")) t.scan_self_hash = std::min(std::max(atoi(e), 0), 2);
     if (const char* e = getenv("COBS_GPU_DEVICE_RANK")) t.device_rank = atoi(e) != 0;
     if (const char* e = getenv("COBS_GPU_TRACE")) t.trace = atoi(e) != 0;
     if (const char* e = getenv("COBS_GPU_ROW_RANGES")) t.row_ranges = atoi(e) != 0;
@@ -586,6 +587,9 @@ cobs_gpu_status cobs_gpu_set_tuning(cobs_gpu_index* ix, const char* key, int64_t
         t.graph = value < 0 ? -1 : value != 0;
     } else if (k == "lds_staged") {
         t.lds_staged = value > 0;
+    } else if (k == "scan_self_hash") {
+        if (value < -1 || value > 2) return fail(COBS_GPU_ERR_ARG, "scan_self_hash: 0 (never), 1 (by table size), 2 (wherever the shape allows)");
+        t.scan_self_hash = value < 0 ? 1 : (int)value;
     } else if (k == "device_rank") {
         t.device_rank = value != 0;
     } else if (k == "rank_window_kib") {
@@ -620,7 +624,7 @@ cobs_gpu_status cobs_gpu_set_tuning(cobs_gpu_index* ix, const char* key, int64_t
         if (value < 0) return fail(COBS_GPU_ERR_ARG, "hit_cap: 0 (the pool's capacity) or a positive record count");
         t.hit_cap = (uint64_t)value;
     } else {
-        return fail(COBS_GPU_ERR_ARG, "unknown tuning key (waves, tile_w, mq, pass_bytes, pipe_chars, graph, lds_staged, device_rank, rank_pack, rank_slim, rank_segments, rank_window_kib, hash_stream, tile_topk, row_fetch, row_fetch_alpha, min_score_bytes, hit_cap)");
+        return fail(COBS_GPU_ERR_ARG, "unknown tuning key (waves, tile_w, mq, pass_bytes, pipe_chars, graph, lds_staged, scan_self_hash, device_rank, rank_pack, rank_slim, rank_segments, rank_window_kib, hash_stream, tile_topk, row_fetch, row_fetch_alpha, min_score_bytes, hit_cap)");
     }
     return COBS_GPU_OK;
 }

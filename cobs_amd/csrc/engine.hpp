@@ -131,6 +131,12 @@ struct Tuning {
     bool no_pin = false;        // COBS_GPU_NO_PIN: never hipHostRegister the mapped file
     int graph = -1;             // COBS_GPU_GRAPH: captured-graph path for small batches off / on
     bool lds_staged = false;    // COBS_GPU_LDS_STAGED: the LDS-staged scan variant (A/B measurements only)
+    // COBS_GPU_SCAN_SELF_HASH: a pass of the self-hashing shape class (geometry.cpp: self_hash_shape) runs without K1, its
+    // scan work-groups hash their query's terms themselves (kernels.hip: SH).  0: never; 1: where K1's table of one
+    // sub-index is larger than kSelfHashMinTable (the tiles of a sub-index re-read it one tile pass apart; measured: a
+    // 4.03 MB table gains nothing or loses, a 12 MB one gains -- EXPERIMENTS.md "Hashing in the scan work-group");
+    // 2: wherever the shape class allows (tests, A/B)
+    int scan_self_hash = 1;
     uint32_t min_score_bytes = 0;   // 2 / 4: scores at least that wide (the reference's classic_search_disable_8bit / _16bit)
     int row_fetch = 1;          // streamed chunks are fetched row by row when a batch looks up few of their rows (0: always whole)
     uint32_t row_fetch_alpha = 1;   // ... i.e. when alpha x (looked-up bytes) <= the chunk's bytes.  Measured on MI355X: rows of 1568 bytes
@@ -412,6 +418,7 @@ struct cobs_gpu_batch {
     hipEvent_t hashed = nullptr;         // ... and the event K2's stream waits for
     uint64_t run_seq = 0, read_seq = 0;
     uint64_t stats[4] = {0, 0, 0, 0};
+    uint64_t table_bytes = 0;         // K1's table for the current queries (stats[3] of a run that launches K1)
     uint64_t algo_row_bytes = 0;      // gathered row bytes of the current queries (stats[0] adds the score bytes a run writes)
     hipEvent_t run_done = nullptr;    // after the last kernel of the most recent run
     // host-buffer API only: the stream this scratch batch lives on and the event after its pass
@@ -466,6 +473,22 @@ uint64_t slice_bytes(uint64_t sig, uint64_t ncols, const Tuning& tune);
 struct ScanGeom { uint32_t tile_w; int nwaves; bool multi_query; };
 ScanGeom scan_geometry(const Chunk& c, uint64_t mean_blocks, uint64_t max_blocks, uint64_t num_hashes,
                        uint32_t forced_waves, int planes, bool idx64, const Tuning& tune);
+// whether the self-hashing scan's LDS array (kSelfHashEntries) holds the row indices of every tile of the chunk under
+// geometry g, for queries of up to max_blocks 8-term blocks: (sub-indexes a tile lies in) x (max_blocks + 1) x 8 entries
+uint32_t tile_sub_indexes(const Chunk& c, uint32_t tile_w);
+bool self_hash_fits(const Chunk& c, const ScanGeom& g, uint64_t max_blocks);
+// The self-hashing shape class: tuning key scan_self_hash on, and every file of the handle is whole sub-indexes resident in
+// HBM (no budget, no shard cut inside a sub-index, no row ranges) of 31-mers under one hash function with 32-bit row
+// indices, no findere, one query per work-group, and every tile's row indices fit the scan's LDS array.  Part of
+// pass_shape_class.  pass_self_hash: ... and the run writes score rows or hits only (no top-k) and does not take its
+// thresholds from K1's valid positions (invalid_bases = skip with a threshold): such a run launches no K1.
+// (scan_self_hash = 1 also asks for a table of more than kSelfHashMinTable bytes per sub-index in every file.  The value
+// is placed empirically between the two batch sizes that were measured on either side of the break-even, 1000 queries
+// of 1000 terms -- 4.03 MB: even on C3, 2.5 % slower on an index of 245 sub-indexes -- and 3000 -- 12 MB: 4.5 % faster
+// on both; where in between the break-even lies, and which cache level decides it, has not been measured.)
+constexpr uint64_t kSelfHashMinTable = 4ull << 20;
+bool self_hash_shape(const cobs_gpu_batch* b);
+bool pass_self_hash(const cobs_gpu_batch* b, double threshold);
 std::vector<VPage> held_slices(const IndexMeta& m, uint32_t rank, uint32_t count, uint32_t mode);
 cobs_gpu_status plan_part(Part& pt, const cobs_gpu_index* ix);
 cobs_gpu_status chunk_part(Part& pt, uint64_t cap, const Tuning& tune, uint64_t keep_bytes = 0, uint64_t* kept = nullptr);

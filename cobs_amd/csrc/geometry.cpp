@@ -85,4 +85,45 @@ ScanGeom scan_geometry(const Chunk& c, uint64_t mean_blocks, uint64_t max_blocks
     return g;
 }
 
+// The sub-indexes one tile of tile_w chunks can lie in (scan_tile_pages, kernels.hpp: launch_scan holds the same bound).
+uint32_t tile_sub_indexes(const Chunk& c, uint32_t tile_w) { return scan_tile_pages(c.pages.size(), c.cpp, tile_w); }
+
+// The self-hashing scan hashes for every sub-index of its tile, while they fit its LDS array; a pass with a tile they do
+// not fit stays on K1's table as a whole (self_hash_shape).
+bool self_hash_fits(const Chunk& c, const ScanGeom& g, uint64_t max_blocks) {
+    if (g.multi_query) return false;
+    return scan_self_hash_fits(c.pages.size(), c.cpp, g.tile_w, max_blocks);
+}
+
+// Which passes take the self-hashing form (engine.hpp).  Host arithmetic over the batch and the plan only, like the rest of
+// this file: tests/host/self_hash_select.cpp compiles it into a program without the HIP runtime.
+bool self_hash_shape(const cobs_gpu_batch* b) {
+    const ::cobs_gpu_index* ix = b->ix;
+    const size_t nq = b->nq;
+    if (ix->tune.scan_self_hash == 0 || nq == 0 || b->findere != 0 || ix->hbm_budget != 0 || ix->tune.lds_staged) return false;
+    for (size_t f = 0; f < ix->parts.size(); ++f) {
+        const Part& p = ix->parts[f];
+        if (p.streamed || p.has_row_ranges || p.chunks.empty() ||
+            !scan_has_self_hash(b->planes, (uint32_t)p.meta.num_hashes, p.meta.term_size, p.idx64))
+            return false;
+        // the table of ONE sub-index, 32 bytes per block: what the tiles of a sub-index re-read a tile pass apart
+        if (ix->tune.scan_self_hash == 1 && (b->work[f].h_blk_off[nq] + nq) * 32ull <= kSelfHashMinTable) return false;
+        for (const Chunk& c : p.chunks) {
+            if (!c.d_data || c.row_range) return false;
+            for (const VPage& v : c.vp)        // whole sub-indexes only (a shard cut inside one keeps the table)
+                if (v.nrows != 0 || v.col0 != 0 || v.ncols != p.meta.page_row_bytes()) return false;
+            const ScanGeom g = scan_geometry(c, b->work[f].h_blk_off[nq] / nq, (b->max_terms + 7) / 8, p.meta.num_hashes,
+                                             ix->waves_per_group, b->planes, p.idx64, ix->tune);
+            if (!self_hash_fits(c, g, (b->max_terms + 7) / 8)) return false;
+        }
+    }
+    return true;
+}
+
+bool pass_self_hash(const cobs_gpu_batch* b, double threshold) {
+    if (b->topk_k != 0 || b->topk_direct) return false;                                   // score rows or hits only
+    if (threshold > 0.0 && b->invalid_bases == COBS_GPU_INVALID_SKIP) return false;       // thresholds from K1's valid positions
+    return self_hash_shape(b);
+}
+
 }  // namespace cobs_amd

@@ -166,27 +166,10 @@ __global__ __launch_bounds__(256) void hash_kernel_k31(HashArgs a, uint64_t tota
     const RowTableWriter<IdxT> tab(a.table, b0, q, a.npages, H, tblk);
     // the k-mer and one following byte as 8 (unaligned) dwords; the text buffer is padded
     uint32_t f[8];
-    if (i < T) {
-        const uint8_t* p = text + i;
-        const uint32_t mis = (uint32_t)((uintptr_t)p & 3u);
-        const uint32_t* w = reinterpret_cast<const uint32_t*>(p - mis);
-        uint32_t r[9];
-#pragma unroll
-        for (int j = 0; j < 9; ++j) r[j] = w[j];
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-            f[j] = mis == 0 ? r[j] : (uint32_t)(((uint64_t)r[j] | ((uint64_t)r[j + 1] << 32)) >> (8 * mis));
-        f[7] &= 0x00FFFFFFu;                      // byte 31 is not part of the 31-mer
-    }
+    if (i < T) load31(text + i, f);
     bool term_ok = true;
     if (lenient) {
-        if (i < T) {
-            // (the masked top byte of f[7] stands in as an 'A': the character behind the k-mer does not decide on it)
-            bool good = all_acgt(f[7] | 0x41000000u);
-#pragma unroll
-            for (int j = 0; j < 7; ++j) good = good && all_acgt(f[j]);
-            term_ok = good;
-        }
+        if (i < T) term_ok = valid31(f);
         if (a.valid != nullptr) add_valid_position(a.valid, q, i < T && term_ok && window_tail_valid(text + i + 31u, i, T, a.findere));
     }
     if (i >= T || !term_ok) {
@@ -197,9 +180,7 @@ __global__ __launch_bounds__(256) void hash_kernel_k31(HashArgs a, uint64_t tota
         return;
     }
     uint32_t c[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) c[j] = f[j];
-    if (a.canonicalize != 0) canon31(f, c);
+    term31(f, a.canonicalize != 0, c);
     for (uint32_t j = 0; j < H; ++j) {
         const uint64_t h = xxh64_31(c, (uint64_t)j);
         for (uint32_t p = 0; p < a.npages; ++p) {

@@ -9,7 +9,7 @@
 // gathered row costs ~4.4 VALU ops per 32 documents and the kernel stays on the HBM roofline.
 //
 // The file holds the device code of scan_kernel, its launch templates, and -- as a translation unit of its own -- the
-// plain (FZ = false) instantiations, the LDS-staged ones among them, launch_scan and the scan_* predicates.
+// plain (FZ = false) instantiations, the LDS-staged ones among them, launch_scan (the scan_has_* predicates it dispatches by are in kernels.hpp).
 // scan_findere.hip includes it with COBS_SCAN_FINDERE_UNIT defined and instantiates the findere (FZ = true) kernels, so
 // no instantiation exists in both objects.  The device code stays in THIS file because bench.py keys the replay of
 // profiles/traffic.json on a hash of kernels.hip and geometry.cpp: the hash has to see the scan kernel.
@@ -22,6 +22,7 @@
 #include "device_types.hpp"
 #include "kernels.hpp"
 #include "row_table.hpp"     // K1's row-index table: K2's reader
+#include "term_hash.hpp"     // load31 .. xxh64_31, fast_mod: the self-hashing instantiations (SH) hash as K1 does
 #include "wave_ops.hpp"      // dpp_mov and its control constants, csa, pool_append
 
 namespace cobs_amd {
@@ -267,10 +268,12 @@ __device__ __forceinline__ void glds_rows(const uint8_t* lane_base, uint32_t pit
 // LDS bytes in front of the expansion table / tile metadata: the merge buffers of the waves
 // ([NW/2 (min 1)][NP][64 lanes] of uint4), the row staging ring of the LDS-staged variant, or --
 // 8-bit scores -- the score staging buffer of the epilogue, whichever is largest
-template <int NP, int NW, size_t OutBytes, bool LDSS>
+// (SH: ... or the row indices the work-group hashed for itself, which the merge buffers alias)
+template <int NP, int NW, size_t OutBytes, bool LDSS, bool SH = false>
 __host__ __device__ constexpr size_t scan_lds_front() {
     size_t f = LDSS ? (size_t)NW * 16384 : (size_t)(NW >= 2 ? NW / 2 : 1) * NP * 64 * sizeof(uint4);
     if (OutBytes == 1 && f < 64 * 144) f = 64 * 144;
+    if (SH && f < kSelfHashEntries * sizeof(uint32_t)) f = kSelfHashEntries * sizeof(uint32_t);
     return f;
 }
 
@@ -458,16 +461,26 @@ __device__ __forceinline__ void tile_topk(const ScanArgs& a, const uint32_t (&pl
 // FZ: findere (ScanArgs::findere = z > 0) -- every term's presence words become window words (fz_window) before the
 // counter tree, and a virtual wave walks a CONTIGUOUS range of the query's blocks, primed with the z terms in front of
 // it (loaded, not counted).  Left to the compiler's register budget (the deficit planes cost 12 VGPRs).
-template <int NP, int NW, bool H1, typename OutT, bool MQ, typename IdxT, bool LDSS = false, bool TK = false, bool FZ = false>
-__global__ __launch_bounds__(NW * 64, (!FZ && ((TK && H1) || (!H1 && sizeof(IdxT) == 4 && !LDSS && (NW <= 2 || TK))) && NP <= 10) ? 4 : 1) void scan_kernel(ScanArgs a) {
+// SH: self-hashing (ScanArgs::self_hash; H = 1, 31-mers, 32-bit indices, one query per group, score / hit epilogues).  There is
+// no table from K1: during set-up the NW * 64 threads hash the query's terms -- load31, canon31, xxh64_31, fast_mod, K1's
+// own device functions (term_hash.hpp) -- once per term, and reduce the hash by the signature size of EVERY sub-index the
+// tile's chunks lie in (usually one; a narrow page under a wide tile: several) into an LDS array [sub-index][block + padding
+// block][8].  An invalid term (invalid_bases != 0) and the padding terms name the zero row, as in K1's table.  The row loop
+// takes its two Idx8 reads per trip from LDS: LDS index read | 8 row loads | CSA, the VMEM queue holds row loads only (the
+// compiler counts them).  The array aliases the merge buffers, so a barrier separates the row loop from the merge.  Tile 0 of
+// a launch with ScanArgs::record set reports what K1 reports: the first query with an invalid base, the valid positions.
+template <int NP, int NW, bool H1, typename OutT, bool MQ, typename IdxT, bool LDSS = false, bool TK = false, bool FZ = false,
+          bool SH = false>
+__global__ __launch_bounds__(NW * 64, (!FZ && (SH || (TK && H1) || (!H1 && sizeof(IdxT) == 4 && !LDSS && (NW <= 2 || TK))) && NP <= 10) ? 4 : 1) void scan_kernel(ScanArgs a) {
     static_assert(!(FZ && LDSS), "findere: no LDS-staged variant");
+    static_assert(!SH || (H1 && !MQ && !LDSS && !TK && !FZ && sizeof(IdxT) == 4), "self-hashing: H = 1, one query per group, 32-bit indices, score / hit epilogues");
     // row loads stay temporal: non-temporal loads measured 18 % slower (they bypass the Infinity Cache)
     constexpr bool NT = false;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     // merge buffers: [NW/2 (min 1)][NP][64 lanes] of uint4, then the 256-entry expansion table.
     // LDSS: the front of the buffer is the row staging ring (2 x 8 KiB per wave); the merge
     // buffers, needed only after the row loop, alias it.
-    constexpr size_t kFront = scan_lds_front<NP, NW, sizeof(OutT), LDSS>();
+    constexpr size_t kFront = scan_lds_front<NP, NW, sizeof(OutT), LDSS, SH>();
     static_assert(!LDSS || kFront >= (size_t)(NW >= 2 ? NW / 2 : 1) * NP * 64 * sizeof(uint4), "ring holds the merge buffers");
     uint4* mbuf = reinterpret_cast<uint4*>(smem);
     // 16/32-bit scores expand their planes through a 256-entry table; 8-bit scores transpose in
@@ -535,6 +548,54 @@ __global__ __launch_bounds__(NW * 64, (!FZ && ((TK && H1) || (!H1 && sizeof(IdxT
     // (the loops below walk blocks from this pointer with their own offsets, b * 8 * H: rt.block(b), spelled out where
     // the software-pipelined loads take raw addresses)
     const IdxT* tab = rt.base;
+    const uint32_t* sidx = nullptr;                              // SH: this lane's sub-index in the LDS array
+    if constexpr (SH) {
+        // (nothing is read through `tab`: the block count above is all this form takes from K1's bookkeeping)
+        // the query's terms, hashed here: [sub-index of the tile][nblk_q + 1 blocks][8] in LDS
+        uint32_t* const sh = reinterpret_cast<uint32_t*>(smem);
+        const uint32_t len = a.q_len[q];
+        const uint32_t T = len - 30u;                            // (31-mers; the host refuses shorter queries): nblk_q = ceil(T / 8)
+        const uint32_t stride = (nblk_q + 1u) * 8u;
+        const uint32_t c0 = a.chunk_begin + tile * W;
+        const uint32_t pg0 = c0 / a.cpp, pg1 = (min(c0 + W, a.chunk_end) - 1u) / a.cpp;      // sub-indexes of the tile
+        // (launch_scan refuses this form where the array does not hold every tile's indices -- scan_self_hash_fits,
+        // kernels.hpp --, so this never holds for a launched grid; it keeps the writes below inside the array)
+        if ((pg1 - pg0 + 1u) * stride > kSelfHashEntries) return;
+        const uint8_t* text = a.text + a.span_off[q];
+        const bool canon = a.canonicalize != 0;
+        const bool lenient = canon && a.invalid_bases != 0;
+        const bool rec = a.record != 0u && tile == 0u;
+        uint32_t nvalid = 0u;
+        bool bad = false;
+        for (uint32_t i = threadIdx.x; i < stride; i += NW * 64) {
+            bool ok = i < T;
+            uint64_t h = 0;
+            if (ok) {
+                uint32_t f[8];
+                load31(text + i, f);
+                if (lenient || (rec && canon)) {
+                    const bool good = valid31(f);
+                    if (lenient) { ok = good; nvalid += good ? 1u : 0u; } else bad = bad || !good;
+                }
+                if (ok) {
+                    uint32_t c[8];
+                    term31(f, canon, c);
+                    h = xxh64_31(c, 0);
+                }
+            }
+            for (uint32_t sp = pg0; sp <= pg1; ++sp) {
+                const uint64_t sig = a.pages[sp].sig;
+                sh[(sp - pg0) * stride + i] = ok ? (uint32_t)fast_mod(h, sig, a.pages[sp].magic) : (uint32_t)sig;
+            }
+        }
+        if (rec) {
+            // every character of a query lies in some term: a query holds an invalid character iff one of its terms does
+            if (bad) atomicMax(a.err_query, 0xFFFFFFFFu - q);
+            if (lenient && a.valid != nullptr && nvalid != 0u) atomicAdd(a.valid + q, nvalid);
+        }
+        __syncthreads();
+        sidx = sh + (pg - pg0) * stride;
+    }
     const uint32_t vw = MQ ? wave : wave * G + grp;  // virtual wave of this lane
     const uint32_t NV = MQ ? (uint32_t)NW : NW * G;
     // findere: blocks [fz_first, fz_first + fz_per) of the query (a sliding window needs its terms in order)
@@ -645,6 +706,40 @@ __global__ __launch_bounds__(NW * 64, (!FZ && ((TK && H1) || (!H1 && sizeof(IdxT
             }
         }
         __syncthreads();                   // the merge buffers alias the rings: every wave is done reading
+    } else if constexpr (SH) {
+        // The H = 1 pipeline below with the row indices read from the LDS array: LDS index read and row loads of trip i+1 |
+        // CSA of trip i.  The VMEM queue holds row loads only, 8..16 of them at every wait (the compiler counts them).
+        auto lds_idx8 = [&](uint32_t i) {
+            const uint32_t bidx = vw + i * NV;
+            const uint4* t = reinterpret_cast<const uint4*>(sidx + (bidx < nblk ? bidx : nblk_q) * 8u);
+            return Idx8<uint32_t>{t[0], t[1]};
+        };
+        if (nw > 0) {
+            uint4 XA[8], XB[8];
+            // (the indices of a trip are read right where its rows are issued: a prefetched set, as the table path keeps,
+            // put these instantiations at 134 VGPRs -- three waves per SIMD --, or at 128 with 9 spills in this loop;
+            // read in place they take 121 and no scratch.  The LDS read is short beside the 8 row loads in flight.)
+            issue_rows<NT>(XA, lane_base, pitch, lds_idx8(0));
+            uint32_t i = 0;
+            for (; i + 2 < nw; i += 2) {
+                // XA in flight = trip i
+                issue_rows<NT>(XB, lane_base, pitch, lds_idx8(i + 1));
+                absorb_block<NP>(pl, XA, ea);
+                issue_rows<NT>(XA, lane_base, pitch, lds_idx8(i + 2));
+                absorb_block<NP>(pl, XB, eb);
+                retire_pair<NP>(pl, ea, eb);
+            }
+            if (i + 1 < nw) {
+                issue_rows<NT>(XB, lane_base, pitch, lds_idx8(i + 1));
+                absorb_block<NP>(pl, XA, ea);
+                absorb_block<NP>(pl, XB, eb);
+                retire_pair<NP>(pl, ea, eb);
+            } else {
+                absorb_block<NP>(pl, XA, ea);
+                retire_single<NP>(pl, ea);
+            }
+        }
+        __syncthreads();                   // the merge buffers alias the index array: every wave is done reading
     } else if constexpr (H1) {
         // Three-stage software pipeline, branch-free in the steady state:
         //   row indices of trip i+2 | row loads of trip i+1 | CSA of trip i
@@ -1085,16 +1180,16 @@ __global__ __launch_bounds__(NW * 64, (!FZ && ((TK && H1) || (!H1 && sizeof(IdxT
 // LDS-staged, tile top-k, findere).  This file instantiates the FZ = false ones, scan_findere.hip the FZ = true ones.
 
 template <int NP, int NW, bool H1, typename OutT, bool MQ = false, typename IdxT = uint32_t, bool LDSS = false, bool TK = false,
-          bool FZ = false>
+          bool FZ = false, bool SH = false>
 static hipError_t launch_scan_inst(const ScanArgs& a, hipStream_t stream) {
     const uint32_t per_group = MQ ? 64u / a.tile_w : 1u;
     const uint64_t groups = (uint64_t)((a.chunk_end - a.chunk_begin + a.tile_w - 1) / a.tile_w) *
                             ((a.nq + per_group - 1u) / per_group);
     if (groups == 0) return hipSuccess;
     if (groups > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    constexpr size_t front = scan_lds_front<NP, NW, sizeof(OutT), LDSS>();
+    constexpr size_t front = scan_lds_front<NP, NW, sizeof(OutT), LDSS, SH>();
     constexpr size_t lds = front + (sizeof(OutT) == 1 ? 0 : 256 * sizeof(uint4)) + 64 * 4 * sizeof(uint32_t);
-    auto kern = scan_kernel<NP, NW, H1, OutT, MQ, IdxT, LDSS, TK, FZ>;
+    auto kern = scan_kernel<NP, NW, H1, OutT, MQ, IdxT, LDSS, TK, FZ, SH>;
     if (lds > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -1182,18 +1277,15 @@ int scan_planes_for(uint64_t max_terms) {
     return -1;
 }
 
-bool scan_has_multi_query(int planes, uint32_t num_hashes, uint32_t tile_w) {
-    return num_hashes == 1 && tile_w < 64 && (planes == 4 || planes == 8 || planes == 10 || planes == 12);
-}
-
-bool scan_has_tile_topk(uint32_t num_hashes, bool idx64) { (void)num_hashes; return !idx64; }
-
-bool scan_has_lds_staged(int planes, uint32_t num_hashes, int nw) {
-    return num_hashes == 1 && planes == 10 && (nw == 2 || nw == 4);
+template <int NP, typename OutT>
+static hipError_t launch_scan_sh(const ScanArgs& a, int nw, hipStream_t stream) {
+    if (nw == 1) return launch_scan_inst<NP, 1, true, OutT, false, uint32_t, false, false, false, true>(a, stream);
+    if (nw == 2) return launch_scan_inst<NP, 2, true, OutT, false, uint32_t, false, false, false, true>(a, stream);
+    return launch_scan_inst<NP, 4, true, OutT, false, uint32_t, false, false, false, true>(a, stream);
 }
 
 
-hipError_t launch_scan(const ScanArgs& a, uint32_t ntiles, int planes, int nw, bool multi_query,
+hipError_t launch_scan(const ScanArgs& a, uint32_t ntiles, int planes, int nw, bool multi_query, uint64_t max_blocks,
                        hipStream_t stream) {
     (void)ntiles;
     if (a.cand && (a.lds_staged || a.topk_k == 0 || !scan_has_tile_topk(a.num_hashes, a.idx64 != 0))) return hipErrorInvalidValue;
@@ -1202,6 +1294,17 @@ hipError_t launch_scan(const ScanArgs& a, uint32_t ntiles, int planes, int nw, b
         if (multi_query || a.idx64 || !scan_has_lds_staged(planes, a.num_hashes, nw)) return hipErrorInvalidValue;
         return nw == 2 ? launch_scan_inst<10, 2, true, uint16_t, false, uint32_t, true>(a, stream)
                        : launch_scan_inst<10, 4, true, uint16_t, false, uint32_t, true>(a, stream);
+    }
+    if (a.self_hash) {      // the work-groups hash for themselves: no table
+        if (multi_query || a.cand || a.findere || !a.text || !scan_has_self_hash(planes, a.num_hashes, 31u, a.idx64 != 0)) return hipErrorInvalidValue;
+        // (the bound the work-groups test before they write their LDS array, for the longest query and the widest tile)
+        if (!scan_self_hash_fits(a.npages, a.cpp, a.tile_w, max_blocks)) return hipErrorInvalidValue;
+        switch (planes) {
+        case 4: return launch_scan_sh<4, uint8_t>(a, nw, stream);
+        case 8: return launch_scan_sh<8, uint8_t>(a, nw, stream);
+        case 10: return launch_scan_sh<10, uint16_t>(a, nw, stream);
+        default: return launch_scan_sh<12, uint16_t>(a, nw, stream);
+        }
     }
     // findere: its own instantiations, so that z = 0 launches exactly the plain kernels
     return a.findere ? launch_scan_findere(a, planes, nw, multi_query, stream)

@@ -19,13 +19,40 @@ inline uint32_t scan_score_bytes(int planes) { return planes <= 8 ? 1u : planes 
 
 // K2: ntiles * nq work-groups of nw (1, 2 or 4) waves; multi_query: ntiles * ceil(nq / (64 / tile_w))
 // work-groups whose lane groups serve different queries (short queries; see scan_has_multi_query).
-hipError_t launch_scan(const ScanArgs& a, uint32_t ntiles, int planes, int nw, bool multi_query,
+// max_blocks: the longest query of the batch in 8-term blocks (read by the self-hashing form only, which is refused
+// where a tile's row indices would not fit its LDS array: the kernel itself writes nothing for such a work-group).
+hipError_t launch_scan(const ScanArgs& a, uint32_t ntiles, int planes, int nw, bool multi_query, uint64_t max_blocks,
                        hipStream_t stream);
-bool scan_has_multi_query(int planes, uint32_t num_hashes, uint32_t tile_w);
+// The sub-indexes one tile of tile_w chunks can lie in, of npages sub-indexes cpp chunks wide.  Tiles start at multiples of
+// tile_w: where tile_w divides cpp no tile crosses a boundary; otherwise a tile that starts on a sub-index's last chunk
+// reaches 1 + ceil((tile_w - 1) / cpp) of them (page_size 200 B, 13 chunks: two under W = 8, six under W = 64).
+inline uint32_t scan_tile_pages(uint64_t npages, uint32_t cpp, uint32_t tile_w) {
+    if (npages <= 1 || cpp == 0 || tile_w == 0 || cpp % tile_w == 0) return 1;
+    const uint64_t reach = 1ull + (tile_w - 1ull + cpp - 1ull) / cpp;
+    return (uint32_t)(reach < npages ? reach : npages);
+}
+// ... and whether the self-hashing form's LDS array holds their row indices for queries of up to max_blocks blocks
+inline bool scan_self_hash_fits(uint64_t npages, uint32_t cpp, uint32_t tile_w, uint64_t max_blocks) {
+    return (uint64_t)scan_tile_pages(npages, cpp, tile_w) * (max_blocks + 1) * 8 <= kSelfHashEntries;
+}
+// (which instantiations exist: defined here, so that launch_scan and the host code that picks a variant -- geometry.cpp,
+// pass.cpp and the host-only program under tests/host -- read one definition)
+inline bool scan_has_multi_query(int planes, uint32_t num_hashes, uint32_t tile_w) {
+    return num_hashes == 1 && tile_w < 64 && (planes == 4 || planes == 8 || planes == 10 || planes == 12);
+}
 // run_topk without score rows (ScanArgs::cand): the tile_topk epilogue exists for files with 32-bit row indices
-bool scan_has_tile_topk(uint32_t num_hashes, bool idx64);
+inline bool scan_has_tile_topk(uint32_t num_hashes, bool idx64) { (void)num_hashes; return !idx64; }
 // the LDS-staged A/B variant exists for the headline shape only (H = 1, 10 planes, 2 or 4 waves)
-bool scan_has_lds_staged(int planes, uint32_t num_hashes, int nw);
+inline bool scan_has_lds_staged(int planes, uint32_t num_hashes, int nw) {
+    return num_hashes == 1 && planes == 10 && (nw == 2 || nw == 4);
+}
+// the self-hashing form (ScanArgs::self_hash: no table from K1, the work-groups hash their query's terms into LDS) exists
+// for one hash function over 31-mers, 32-bit row indices and up to 12 planes (2048 terms need 12 at the most: the wider
+// score types never meet the LDS array's limit); launch_scan takes it with multi_query off, no candidate pool, no
+// findere, and only where the LDS array holds the indices of every tile (scan_self_hash_fits)
+inline bool scan_has_self_hash(int planes, uint32_t num_hashes, uint32_t term_size, bool idx64) {
+    return num_hashes == 1 && term_size == 31 && !idx64 && (planes == 4 || planes == 8 || planes == 10 || planes == 12);
+}
 
 // K3: per query the k best (score desc, doc asc) documents with score >= threshold.
 hipError_t launch_topk(const TopkArgs& a, hipStream_t stream);

@@ -228,6 +228,7 @@ cobs_gpu_status cobs_amd::set_queries_on(cobs_gpu_batch* b, const char* const* q
     b->stats[1] = 0;
     b->stats[2] = lookups;
     b->stats[3] = table_bytes;
+    b->table_bytes = table_bytes;
     b->nq = nq;
     if (wait) HIP_TRY(hipStreamSynchronize(up));
     return COBS_GPU_OK;
@@ -266,6 +267,7 @@ uint64_t cobs_amd::pass_shape_class(const cobs_gpu_batch* b) {
             mixin(g.tile_w); mixin((uint64_t)g.nwaves); mixin(g.multi_query);
         }
     }
+    mixin(self_hash_shape(b));     // with or without K1: a graph captured on one path is never replayed on the other
     return key;
 }
 
@@ -360,6 +362,8 @@ cobs_gpu_status cobs_amd::run_impl(cobs_gpu_batch* b, double threshold, size_t t
     // device flags: first invalid query = none, selected hits = 0
     // (a kernel: a captured memset node is not safe to replay, fetch_kernels.hip)
     const bool count_valid = b->invalid_bases != COBS_GPU_INVALID_ERROR && nq;
+    // the self-hashing shape class (tuning key scan_self_hash): this pass launches no K1 and reads no table
+    const bool self_hash = pass_self_hash(b, threshold);
     // invalid_bases = skip: a file's thresholds follow the content of the queries -- made on the device right behind its K1
     // (no host staging: a replayed graph serves other text of its shape class)
     const bool skip_thr = need_thr && b->invalid_bases == COBS_GPU_INVALID_SKIP;
@@ -408,6 +412,7 @@ cobs_gpu_status cobs_amd::run_impl(cobs_gpu_batch* b, double threshold, size_t t
     for (size_t f = 0; f < ix->parts.size(); ++f) {
         Part& p = ix->parts[f];
         if (nq == 0 || p.chunks.empty()) continue;
+        if (self_hash) continue;          // no table: the scan work-groups hash for themselves, and report what K1 reports
         const HashArgs k1 = hash_args_for(b, f, p, nq, b->findere, b->invalid_bases, count_valid ? b->valid.p + f * nq : nullptr);
         if (cobs_gpu_status s = launch_hash_file(b, k1, nq, hs); s != COBS_GPU_OK) return s;
         if (skip_thr) {
@@ -836,6 +841,15 @@ cobs_gpu_status cobs_amd::run_impl(cobs_gpu_batch* b, double threshold, size_t t
                             scan_has_lds_staged(b->planes, (uint32_t)p.meta.num_hashes, nwaves) ? 1u : 0u;
             sa.exp = ix->tune.exp;
             sa.findere = b->findere;
+            sa.text = b->d_text;
+            sa.span_off = b->d_span_off;
+            sa.q_len = b->d_qlen;
+            sa.err_query = b->flags.p;
+            sa.valid = count_valid ? b->valid.p + f * nq : nullptr;
+            sa.self_hash = self_hash ? 1u : 0u;
+            sa.canonicalize = p.meta.canonicalize;
+            sa.invalid_bases = b->invalid_bases;
+            sa.record = ci == 0 ? 1u : 0u;       // once per file and query, as K1: tile 0 of the file's first launch
             sa.chunk_begin = 0;
             sa.chunk_end = c.total_chunks;
             // one launch covers at most 2^31-1 work-groups
@@ -847,7 +861,7 @@ cobs_gpu_status cobs_amd::run_impl(cobs_gpu_batch* b, double threshold, size_t t
                                                           : (uint64_t)ntiles * nq;
                 sa.dbg_every = (uint32_t)std::max<uint64_t>(1, groups / sa.dbg_slots);
             }
-            HIP_TRY(launch_scan(sa, ntiles, b->planes, nwaves, geom.multi_query, st));
+            HIP_TRY(launch_scan(sa, ntiles, b->planes, nwaves, geom.multi_query, (b->max_terms + 7) / 8, st));
             if (!acc_mode) tile_base += ntiles;
             ++launches;
             if (partial) {
@@ -959,6 +973,7 @@ cobs_gpu_status cobs_amd::run_impl(cobs_gpu_batch* b, double threshold, size_t t
     HIP_TRY(hipEventRecord(b->run_done, st));
     b->run_seq++;
     b->stats[1] = launches;
+    b->stats[3] = self_hash ? 0 : b->table_bytes;        // what K1 wrote for this run: nothing when it did not run
     // T * H * (row bytes gathered) + score bytes WRITTEN (a hits-only pass writes none)
     b->stats[0] = b->algo_row_bytes + (b->have_counts ? (uint64_t)nq * ix->local_counts * b->elem_bytes : 0);
     b->ran = true;

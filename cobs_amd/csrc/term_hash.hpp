@@ -167,6 +167,35 @@ __device__ __forceinline__ bool all_acgt(uint32_t w) {
     const uint32_t code = (w >> 1) & 0x03030303u;
     return __builtin_amdgcn_perm(0u, 0x47544341u, code) == w;
 }
+// The 31-mer at p (any alignment; the text buffer is padded) as eight dwords, byte 31 zero: what xxh64_31 / canon31 take.
+__device__ __forceinline__ void load31(const uint8_t* p, uint32_t (&f)[8]) {
+    const uint32_t mis = (uint32_t)((uintptr_t)p & 3u);
+    const uint32_t* w = reinterpret_cast<const uint32_t*>(p - mis);
+    uint32_t r[9];
+#pragma unroll
+    for (int j = 0; j < 9; ++j) r[j] = w[j];
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+        f[j] = mis == 0 ? r[j] : (uint32_t)(((uint64_t)r[j] | ((uint64_t)r[j + 1] << 32)) >> (8 * mis));
+    f[7] &= 0x00FFFFFFu;                      // byte 31 is not part of the 31-mer
+}
+// ... and whether all of its 31 characters are valid bases
+// (the masked top byte of f[7] stands in as an 'A': the character behind the k-mer does not decide on it)
+__device__ __forceinline__ bool valid31(const uint32_t (&f)[8]) {
+    bool good = all_acgt(f[7] | 0x41000000u);
+#pragma unroll
+    for (int j = 0; j < 7; ++j) good = good && all_acgt(f[j]);
+    return good;
+}
+// The 31-mer a term is hashed as: f itself, or (canonicalize) the smaller of f and its reverse complement.  What both
+// hash_kernel_k31 (hash_kernels.hip) and the scan work-groups that hash their query's terms themselves (kernels.hip: SH)
+// hand to xxh64_31.
+__device__ __forceinline__ void term31(const uint32_t (&f)[8], bool canonicalize, uint32_t (&c)[8]) {
+#pragma unroll
+    for (int t = 0; t < 8; ++t) c[t] = f[t];
+    if (canonicalize) canon31(f, c);
+}
+
 __device__ __forceinline__ bool has_newline(uint32_t w) {
     const uint32_t x = w ^ 0x0A0A0A0Au;
     return ((x - 0x01010101u) & ~x & 0x80808080u) != 0u;

@@ -123,7 +123,10 @@ void cobs_gpu_close(cobs_gpu_index* ix);
 /* Per-handle tuning hooks of the scan launch (the COBS_GPU_* environment variables are read once,
  * by cobs_gpu_open*; this changes them afterwards).  key: "waves" (0, 1, 2, 4), "tile_w" (0, 4..64),
  * "mq" (-1 auto, 0, 1), "pass_bytes", "pipe_chars", "graph" (-1 auto, 0, 1), "lds_staged" (0, 1: the
- * measured LDS-staged variant of the scan, headline shape only), "device_rank" / "tile_topk" / "row_fetch" (0 turns the
+ * measured LDS-staged variant of the scan, headline shape only), "scan_self_hash" (0, 1, 2: a pass over whole resident
+ * sub-indexes of 31-mers with one hash function runs without the hash kernel, the scan work-groups hash their query's
+ * terms themselves -- 1, the default: where the hash kernel's table of one sub-index exceeds 4 MiB, 2: wherever the shape
+ * allows, 0: never; COBS_GPU_SCAN_SELF_HASH; EXPERIMENTS.md), "device_rank" / "tile_topk" / "row_fetch" (0 turns the
  * on-device ranking of whole rows / the tile-level top-k / the row-selective out-of-core pass off: A/B and fallback),
  * "row_fetch_alpha", "min_score_bytes" (2 / 4: score rows at least that wide -- the reference's
  * classic_search_disable_8bit / _16bit switches, classic_search.cpp:207-209); "rank_pack" / "rank_slim" / "rank_window_kib" / "rank_segments"

@@ -68,7 +68,12 @@ cobs_gpu_status cobs_gpu_read_rows(const cobs_gpu_index* ix, size_t file_no, uin
  * out[0] = algorithmic bytes of the scan kernel(s): sum over queries of
  *          T * H * (row bytes gathered) + score bytes written
  * out[1] = number of scan-kernel launches, out[2] = k-mer lookups (sum T),
- * out[3] = bytes of row-index table written by K1 and read by K2.            */
+ * out[3] = bytes of row-index table written by K1 and read by K2 IN THIS RUN: 0 for a
+ *          run whose scan work-groups hashed their query's terms themselves (tuning
+ *          key "scan_self_hash"; no K1 launch).  The table's memory stays reserved
+ *          by cobs_gpu_batch_set_queries either way -- the other call families and
+ *          a run of the same batch on the table path use it --, so this is traffic,
+ *          not footprint.                                                          */
 cobs_gpu_status cobs_gpu_batch_stats(const cobs_gpu_batch* b, uint64_t out[4]);
 /* HIP-event duration (ms) of the scan kernel(s) / hash kernel, averaged over the
  * runs since the previous call (at most the last 64); events are recorded on the

@@ -17,6 +17,8 @@ def main():
     configs = [dict(kv.split("=") for kv in c.split(",") if kv) for c in sys.argv[2:]] or [{}]
     if shape == "c3":
         cfg, nq, kmers = bench.c3_config(), 10000, 1000
+    elif shape.startswith("c3q"):       # the C3 index under a batch of another size: c3q1000
+        cfg, nq, kmers = bench.c3_config(), int(shape[3:]), 1000
     elif shape == "c3short":
         cfg, nq, kmers = bench.c3_config(), 20000, 100
     elif shape.startswith("reads"):
@@ -57,6 +59,7 @@ def main():
     configs = [{alias.get(k, k): v for k, v in c.items()} for c in configs]
     keys = sorted({k for c in configs for k in c})
     times = [[] for _ in configs]
+    both = [[] for _ in configs]          # scan + hash kernel time (a change that moves work between the two)
     for rnd in range(7):
         for ci, c in enumerate(configs):
             for k in keys:
@@ -66,14 +69,21 @@ def main():
             for _ in range(3):
                 b.run(0.0)
             b.sync()
-            ms = b.kernel_ms()["scan_ms"]
+            km = b.kernel_ms()
             if rnd > 0:
-                times[ci].append(ms)
+                times[ci].append(km["scan_ms"])
+                both[ci].append(km["scan_ms"] + km["hash_ms"])
     st = b.stats()
-    for c, t in zip(configs, times):
+    for c, t, sh in zip(configs, times, both):
         med = statistics.median(t)
-        print("%-50s scan median %.3f ms  min %.3f  max %.3f   %.1f GB/s" %
-              (c, med, min(t), max(t), st["algorithmic_bytes"] / med / 1e6))
+        print("%-50s scan median %.3f ms  min %.3f  max %.3f   %.1f GB/s   scan+hash median %.3f ms" %
+              (c, med, min(t), max(t), st["algorithmic_bytes"] / med / 1e6, statistics.median(sh)))
+    # the same configuration given twice is the in-process noise band of this run
+    for i in range(len(configs)):
+        for j in range(i + 1, len(configs)):
+            if configs[i] == configs[j]:
+                a, d = statistics.median(both[i]), statistics.median(both[j])
+                print("noise band (config %d vs %d, identical): %.3f ms = %.2f %%" % (i, j, abs(a - d), 100 * abs(a - d) / a))
 
 
 if __name__ == "__main__":

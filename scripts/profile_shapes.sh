@@ -30,7 +30,15 @@ declare -A SHAPES=(
   [c3top10rows]="--num-results 10 --topk-with-rows"
   [reads100top10]="--queries 40000 --kmers 70 --num-results 10"
 )
-FULL="c3 c3q256 c3x8 reads50"
+FULL=${PROFILE_FULL-"c3 c3q256 c3x8 reads50"}      # (PROFILE_FULL="": the trace and the FETCH_SIZE / WRITE_SIZE passes only)
+# every profiled process under a time limit of its own; the first one that fails ends the script (nothing more is
+# started on a device after a fault or a hang)
+run() {
+  local log=$1; shift
+  timeout -k 10 900 "$@" > "$log" 2>&1
+  local rc=$?
+  if [ $rc -ne 0 ]; then echo "profile_shapes: exit $rc from: $* (see $log)"; tail -20 "$log"; exit $rc; fi
+}
 WANT=${*:-c3 c3q256 c3x8 c3x8q2500 c2 c4 c3h3 reads50 reads100 reads150 c3hits reads100hits c3top10 c3top10rows reads100top10}
 cd /tmp
 for shape in $WANT; do
@@ -38,17 +46,17 @@ for shape in $WANT; do
   D="$OUT/$shape"
   mkdir -p "$D"
   BENCH="python $REPO/bench.py --no-cpu-baseline --steps 5 --warmup 2 $EXTRA"
-  rocprofv3 --kernel-trace --stats --output-format csv -d "$D/trace" -o bench -- $BENCH > "$D/trace.log" 2>&1
+  run "$D/trace.log" rocprofv3 --kernel-trace --stats --output-format csv -d "$D/trace" -o bench -- $BENCH
   SHORT="python $REPO/bench.py --no-cpu-baseline --steps 2 --warmup 1 $EXTRA"
-  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$D/pmc_fetch" -o bench -- $SHORT > "$D/pmc_fetch.log" 2>&1
-  rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d "$D/pmc_write" -o bench -- $SHORT > "$D/pmc_write.log" 2>&1
+  run "$D/pmc_fetch.log" rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$D/pmc_fetch" -o bench -- $SHORT
+  run "$D/pmc_write.log" rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d "$D/pmc_write" -o bench -- $SHORT
   if [[ " $FULL " == *" $shape "* ]]; then
     # memory-side request counters of the L2: all requests vs those "destined for DRAM" (do Infinity-Cache hits separate? r04: no)
-    rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_DRAM_sum TCC_EA0_RDREQ_32B_sum --kernel-trace --output-format csv -d "$D/pmc_ea_rd" -o bench -- $SHORT > "$D/pmc_ea_rd.log" 2>&1
-    rocprofv3 --pmc TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_DRAM_sum TCC_EA0_WRREQ_64B_sum --kernel-trace --output-format csv -d "$D/pmc_ea_wr" -o bench -- $SHORT > "$D/pmc_ea_wr.log" 2>&1
-    rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum --kernel-trace --output-format csv -d "$D/pmc_tcc" -o bench -- $SHORT > "$D/pmc_tcc.log" 2>&1
-    rocprofv3 --pmc SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d "$D/pmc_sq" -o bench -- $SHORT > "$D/pmc_sq.log" 2>&1
-    rocprofv3 --pmc SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SALU --kernel-trace --output-format csv -d "$D/pmc_lds" -o bench -- $SHORT > "$D/pmc_lds.log" 2>&1
+    run "$D/pmc_ea_rd.log" rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_DRAM_sum TCC_EA0_RDREQ_32B_sum --kernel-trace --output-format csv -d "$D/pmc_ea_rd" -o bench -- $SHORT
+    run "$D/pmc_ea_wr.log" rocprofv3 --pmc TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_DRAM_sum TCC_EA0_WRREQ_64B_sum --kernel-trace --output-format csv -d "$D/pmc_ea_wr" -o bench -- $SHORT
+    run "$D/pmc_tcc.log" rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum --kernel-trace --output-format csv -d "$D/pmc_tcc" -o bench -- $SHORT
+    run "$D/pmc_sq.log" rocprofv3 --pmc SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d "$D/pmc_sq" -o bench -- $SHORT
+    run "$D/pmc_lds.log" rocprofv3 --pmc SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SALU --kernel-trace --output-format csv -d "$D/pmc_lds" -o bench -- $SHORT
   fi
   grep -h '"metric"' "$D/trace.log" | tail -1 | cut -c1-200
 done
