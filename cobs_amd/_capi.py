@@ -51,6 +51,11 @@ class GroupHit(C.Structure):
     _fields_ = [("file_no", C.c_uint32), ("doc", C.c_uint32), ("score", C.c_uint32), ("votes", C.c_uint32)]
 
 
+class BestHit(C.Structure):
+    _fields_ = [("file_no", C.c_uint32), ("doc", C.c_uint32), ("query", C.c_uint32), ("score", C.c_uint32),
+                ("positions", C.c_uint32), ("ties", C.c_uint32)]
+
+
 class SetHit(C.Structure):
     _fields_ = [("file_no", C.c_uint32), ("set", C.c_uint32), ("any", C.c_uint32), ("all", C.c_uint32)]
 
@@ -199,6 +204,10 @@ SYMBOLS = {
     "cobs_gpu_search_groups": (_int, [_vp, C.POINTER(_cp), C.POINTER(_sz), _sz, C.POINTER(_sz), _sz, _dbl, _dbl, _sz,
                                       C.POINTER(GroupHit), _sz, C.POINTER(_sz), _pu64, C.POINTER(_sz)]),
     "cobs_gpu_groups_ms": (_int, [_vp, C.POINTER(C.c_double * 3)]),
+    "cobs_gpu_search_best": (_int, [_vp, C.POINTER(_cp), C.POINTER(_sz), _sz, C.POINTER(_sz), _sz, _dbl, _sz,
+                                    C.POINTER(BestHit), _sz, C.POINTER(_sz), C.POINTER(_sz)]),
+    "cobs_gpu_best_ms": (_int, [_vp, C.POINTER(C.c_double * 3)]),
+    "cobs_gpu_best_counts": (_int, [_vp, C.POINTER(C.c_uint64 * 4)]),
     "cobs_gpu_doc_bits": (_int, [_vp, _sz, C.POINTER(_u64), _sz, C.POINTER(_sz)]),
     "cobs_gpu_doc_bits_ms": (_int, [_vp, C.POINTER(C.c_double * 4)]),
     "cobs_gpu_doc_bits_probe_ms": (_int, [_vp, _sz, C.POINTER(C.c_double)]),

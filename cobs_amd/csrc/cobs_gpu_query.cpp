@@ -42,6 +42,16 @@ static void usage() {
                  "        one line *<name of its first record><TAB><hits>, then doc_name<TAB>sum<TAB>votes for the documents whose\n"
                  "        summed score reaches -t of the group's positions; votes = the group's records that reach\n"
                  "        --read-threshold X (default 0) in the document; not with several devices or --hbm-budget\n"
+                 "       [--best N|all | --best-by-name SEP]\n"
+                 "       --best N: typing -- every N consecutive records of the query file are one group (all: the whole file), the\n"
+                 "        alleles of a locus; per group one line *<name of its first record><TAB><hits>, then per document\n"
+                 "        doc_name<TAB>best record's name<TAB>score<TAB>positions<TAB>ties: the record of the group that fits the\n"
+                 "        document best (the largest score / positions), for the documents where it reaches -t of its own positions;\n"
+                 "        ties = the group's records that fit equally well (honours -l, --findere and --invalid-bases)\n"
+                 "       --best-by-name SEP: the same with the groups formed from the names: the maximal runs of consecutive records\n"
+                 "        whose name up to the last SEP (one character) is equal (adk_1 adk_2 fumC_1: two groups with _); a name\n"
+                 "        without SEP is its own group; the header line carries *<that prefix>.  Neither with several devices,\n"
+                 "        --hbm-budget, --group, --sets, --weighted, --coverage, --window, --prevalence, --positions or --fpr-adjust.\n"
                  "       --positions: every result line gets a tab and one character per position of the query in that\n"
                  "        document, position 0 first: 1 = the k-mer there (with --findere Z: all Z + 1 from there) is present;\n"
                  "        the number of 1s is the score.  Not with several devices or --hbm-budget.\n"
@@ -510,6 +520,8 @@ int main(int argc, char** argv) {
     bool sets_profile = false;               // --sets-profile
     std::string group;                       // --group N|all
     double read_threshold = 0.0;             // --read-threshold X
+    std::string best, best_sep;              // --best N|all, --best-by-name SEP
+    bool best_by_name = false;
     unsigned num_kmers = 1000, num_queries = 10000, num_warmup = 100;
     size_t seed = std::random_device{}();
     for (int i = 1; i < argc; ++i) {
@@ -576,6 +588,8 @@ int main(int argc, char** argv) {
         else if (a == "--sets-profile") sets_profile = true;
         else if (a == "--group") group = need("--group");
         else if (a == "--read-threshold") read_threshold = std::atof(need("--read-threshold"));
+        else if (a == "--best") best = need("--best");
+        else if (a == "--best-by-name") { best_sep = need("--best-by-name"); best_by_name = true; }
         else if (a == "-h" || a == "--help") { usage(); return 0; }
         else if (!a.empty() && a[0] == '-') { std::fprintf(stderr, "unknown flag %s\n", a.c_str()); usage(); return 1; }
         else if (fpr_mode && index_paths.empty()) index_paths.push_back(a);
@@ -616,6 +630,21 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "--coverage: not with several devices (-d A,B / --sharded) or --hbm-budget (the rows have to be "
                              "resident on one GPU), nor with --positions, --prevalence, --weighted, --sets, --fpr-adjust or --group\n");
         return 1;
+    }
+    size_t best_size = 0;                    // 0 with --best all and --best-by-name
+    if (!best.empty() || best_by_name) {
+        char* end = nullptr;
+        const unsigned long long n = std::strtoull(best.c_str(), &end, 10);
+        if (!best.empty() && best != "all" && (*end != '\0' || n == 0)) { std::fprintf(stderr, "--best: a number of records > 0, or all\n"); return 1; }
+        if (best_by_name && best_sep.size() != 1) { std::fprintf(stderr, "--best-by-name: one separator character\n"); return 1; }
+        best_size = best.empty() || best == "all" ? 0 : (size_t)n;
+        if ((!best.empty() && best_by_name) || devices.size() > 1 || force_sharded || hbm_budget != 0 || query_file.empty() || !group.empty() ||
+            !sets_file.empty() || weighted || coverage || window || prevalence || positions || fpr_adjust) {
+            std::fprintf(stderr, "--best / --best-by-name: one of the two; needs a query file (-f); not with several devices (-d A,B / "
+                                 "--sharded) or --hbm-budget, nor with --group, --sets, --weighted, --coverage, --window, --prevalence, "
+                                 "--positions or --fpr-adjust\n");
+            return 1;
+        }
     }
     if (!sets_by.empty() && sets_by != "any" && sets_by != "all") { std::fprintf(stderr, "--sets-by: any or all\n"); return 1; }
     if (!sets_by.empty() && sets_file.empty()) { std::fprintf(stderr, "--sets-by: needs --sets FILE.tsv\n"); return 1; }
@@ -855,6 +884,43 @@ int main(int argc, char** argv) {
             for (size_t g = 0; g + 1 < offs.size(); ++g) {
                 std::cout << comments[offs[g]] << '\t' << results[g].size() << '\n';
                 for (const auto& r : results[g]) std::cout << r.doc_name << '\t' << r.score << '\t' << r.votes << '\n';
+            }
+            std::cout.flush();
+            print_timer(s);
+            return 0;
+        }
+        if (!best.empty() || best_by_name) {
+            // a record's name: its comment line without the marker, up to the first blank
+            std::vector<std::string> names;
+            for (const std::string& c : comments) {
+                const std::string s = c.empty() ? c : c.substr(1);
+                names.push_back(s.substr(0, s.find_first_of(" \t")));
+            }
+            std::vector<size_t> offs{0};
+            std::vector<std::string> labels;
+            if (best_by_name) {
+                auto prefix = [&](const std::string& s) { const size_t p = s.rfind(best_sep[0]); return p == std::string::npos ? s : s.substr(0, p); };
+                for (size_t q = 0; q < queries.size(); ++q) {
+                    const bool open = names[q].find(best_sep[0]) != std::string::npos;
+                    if (q > 0 && open && names[q - 1].find(best_sep[0]) != std::string::npos && prefix(names[q]) == labels.back()) continue;
+                    if (q > 0) offs.push_back(q);
+                    labels.push_back(prefix(names[q]));
+                }
+                if (!queries.empty()) offs.push_back(queries.size());
+                for (std::string& l : labels) l = "*" + l;
+            } else {
+                const size_t step = best_size ? best_size : std::max<size_t>(queries.size(), 1);
+                for (size_t q = 0; q < queries.size(); q += step) {
+                    labels.push_back(comments[q]);
+                    offs.push_back(std::min(q + step, queries.size()));
+                }
+            }
+            std::vector<std::vector<cobs_gpu::ClassicSearch::BestResult>> results;
+            dynamic_cast<cobs_gpu::ClassicSearch&>(s).search_best(queries, offs, results, threshold, num_results);
+            for (size_t g = 0; g + 1 < offs.size(); ++g) {
+                std::cout << labels[g] << '\t' << results[g].size() << '\n';
+                for (const auto& r : results[g])
+                    std::cout << r.doc_name << '\t' << names[r.query] << '\t' << r.score << '\t' << r.positions << '\t' << r.ties << '\n';
             }
             std::cout.flush();
             print_timer(s);

@@ -167,6 +167,7 @@ cobs_gpu_index::~cobs_gpu_index() {
     if (sets) destroy_sets_work(sets);
     if (coverage) destroy_coverage_work(coverage);
     if (window) destroy_window_work(window);
+    if (best) destroy_best_work(best);
     for (auto* b : scratch) delete b;
     if (xchg_stream) (void)hipStreamDestroy(xchg_stream);
 }

@@ -312,6 +312,7 @@ struct WeightedWork;    // weighted.cpp: cells, weights and hit pool of cobs_gpu
 struct SetsWork;        // sets.cpp: labels, segment records and bitmaps of cobs_gpu_search_sets
 struct CoverageWork;    // coverage.cpp: thresholds and hit pool of cobs_gpu_search_coverage
 struct WindowWork;      // window.cpp: thresholds, windows and hit pool of cobs_gpu_search_window
+struct BestWork;        // best.cpp: scratch batches, best-member state and pool of cobs_gpu_search_best
 
 }  // namespace cobs_amd
 
@@ -341,6 +342,7 @@ struct cobs_gpu_index {
     cobs_amd::SetsWork* sets = nullptr;             // sets.cpp
     cobs_amd::CoverageWork* coverage = nullptr;     // coverage.cpp
     cobs_amd::WindowWork* window = nullptr;         // window.cpp
+    cobs_amd::BestWork* best = nullptr;             // best.cpp
     ~cobs_gpu_index();
 };
 
@@ -600,6 +602,7 @@ void destroy_weighted_work(WeightedWork* w);       // weighted.cpp
 void destroy_sets_work(SetsWork* w);               // sets.cpp
 void destroy_coverage_work(CoverageWork* w);       // coverage.cpp
 void destroy_window_work(WindowWork* w);           // window.cpp
+void destroy_best_work(BestWork* w);               // best.cpp
 void drop_fill_cache(cobs_gpu_index* ix, size_t file_no);   // ... the cached counts of one file (its bits changed)
 bool rank_on_device_applies(const cobs_gpu_batch* b, size_t nq);
 cobs_gpu_status rank_launch(cobs_gpu_batch* b, size_t q_first, size_t nq, size_t limit);

@@ -13,12 +13,10 @@
 #include <algorithm>
 
 #include "group_kernels.hpp"
+#include "score_rows.hpp"
 
 namespace cobs_amd {
 namespace {
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
 // Accumulators are zeroed by a kernel, not a memset node (fetch_kernels.hip, clear_flags_kernel: a captured memset node
 // replayed stale host data; a kernel carries its arguments by value).
@@ -28,25 +26,6 @@ __global__ __launch_bounds__(256) void group_zero_kernel(uint32_t* p, uint64_t n
     u32x4* v = reinterpret_cast<u32x4*>(p);
     for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < nvec; i += stride) v[i] = u32x4{0u, 0u, 0u, 0u};
     for (uint64_t i = nvec * 4u + (uint64_t)blockIdx.x * 256u + threadIdx.x; i < nwords; i += stride) p[i] = 0u;
-}
-
-template <typename ST>
-__device__ __forceinline__ uint32_t score_of(const u32x4& v, uint32_t j) {
-    if (sizeof(ST) == 1) return (v[j / 4u] >> (8u * (j % 4u))) & 0xFFu;
-    if (sizeof(ST) == 2) return (v[j / 2u] >> (16u * (j % 2u))) & 0xFFFFu;
-    return v[j];
-}
-
-// 16 bytes of one score row (rows of u8 scores are 8-byte aligned only: local_counts is a multiple of 8); a lane at the
-// end of a u8 row whose last 8 slots do not exist loads the 8 that do
-__device__ __forceinline__ u32x4 load_scores(const uint8_t* p, bool half) {
-    if (half) {
-        const u32x2 w = *reinterpret_cast<const u32x2*>(p);
-        return u32x4{w[0], w[1], 0u, 0u};
-    }
-    u32x4 v;
-    __builtin_memcpy(&v, __builtin_assume_aligned(p, 8), 16);
-    return v;
 }
 
 template <typename ST>

@@ -17,7 +17,7 @@ import sys
 import numpy as np
 
 from . import _capi
-from ._capi import CobsGpuError, GroupHit, Hit, IndexInfo, Options, SetHit, SetQuorumHit, Synth, check
+from ._capi import BestHit, CobsGpuError, GroupHit, Hit, IndexInfo, Options, SetHit, SetQuorumHit, Synth, check
 
 
 class SearchResult:
@@ -52,6 +52,31 @@ class GroupResult:
     def __eq__(self, other):
         return (isinstance(other, GroupResult) and self.doc_name == other.doc_name and self.score == other.score
                 and self.votes == other.votes)
+
+
+class BestResult:
+    """one document of a group's result (Search.search_best): the group's best query in it -- `query`, its index in the
+    call --, that query's score and the positions the score is out of, and how many of the group's queries fit equally
+    well (ties, the best one included)"""
+    __slots__ = ("doc_name", "file_no", "doc", "query", "score", "positions", "ties")
+
+    def __init__(self, doc_name="", file_no=0, doc=0, query=0, score=0, positions=0, ties=0):
+        self.doc_name = doc_name
+        self.file_no = file_no
+        self.doc = doc
+        self.query = query
+        self.score = score
+        self.positions = positions
+        self.ties = ties
+
+    def _key(self):
+        return (self.doc_name, self.file_no, self.doc, self.query, self.score, self.positions, self.ties)
+
+    def __repr__(self):
+        return "BestResult(doc_name=%r, file_no=%d, doc=%d, query=%d, score=%d, positions=%d, ties=%d)" % self._key()
+
+    def __eq__(self, other):
+        return isinstance(other, BestResult) and self._key() == other._key()
 
 
 class AdjustedResult(SearchResult):
@@ -1256,6 +1281,72 @@ class Search:
         check(self._lib.cobs_gpu_groups_ms(self._h, C.byref(t)))
         return {"accumulate_ms": t[0], "select_ms": t[1], "order_ms": t[2]}
 
+    # -- best of a group: every document's best query of a group ------------------------
+    BEST_HIT_DTYPE = np.dtype([("file_no", "<u4"), ("doc", "<u4"), ("query", "<u4"), ("score", "<u4"), ("positions", "<u4"),
+                               ("ties", "<u4")])
+
+    def search_best_arrays(self, queries, group_offsets=None, threshold=0.0, num_results=0, group_size=None):
+        """cobs_gpu_search_best: group g is queries[group_offsets[g]:group_offsets[g + 1]] (contiguous; n_groups + 1
+        non-decreasing offsets from 0 to len(queries)), or every group_size consecutive queries
+        -> (hit_offsets uint64 [n_groups + 1], hits BEST_HIT_DTYPE): the records of group g are
+        hits[hit_offsets[g]:hit_offsets[g + 1]], one per document whose best query of the group reaches threshold of its
+        own positions, by score / positions descending, then score descending, then (file_no, doc)."""
+        if type(self)._search_batch_call is not Search._search_batch_call:
+            raise CobsGpuError(_capi.ERR_UNSUPPORTED, "best: not on a device-list handle (ask every shard for its documents)")
+        qs = [q if type(q) is bytes else _as_bytes(q) for q in queries]
+        nq = len(qs)
+        if (group_offsets is None) == (group_size is None):
+            raise ValueError("give group_offsets or group_size")
+        if group_offsets is None:
+            if int(group_size) < 1:
+                raise ValueError("group_size needs to be at least 1")
+            group_offsets = list(range(0, nq, int(group_size))) + [nq]
+        goffs = np.ascontiguousarray(group_offsets, dtype=np.uint64)
+        if goffs.ndim != 1 or len(goffs) < 1:
+            raise ValueError("group_offsets needs n_groups + 1 entries")
+        ng = len(goffs) - 1
+        arr = (C.c_char_p * max(nq, 1))(*qs)
+        lens = (C.c_size_t * max(nq, 1))(*[len(q) for q in qs])
+        offs = np.zeros(ng + 1, dtype=np.uint64)
+        bad = C.c_size_t(0)
+        if num_results > 0:
+            cap = ng * min(num_results, self.total_counts)
+        elif threshold <= 0:
+            cap = ng * self.total_counts
+        else:
+            cap = 16 * ng + 1024           # (too small: the call reports the needed size and is made again)
+        cap = max(1, cap)
+        while True:
+            hits = np.zeros(cap, dtype=self.BEST_HIT_DTYPE)
+            st = self._lib.cobs_gpu_search_best(
+                self._h, arr, lens, nq, C.cast(goffs.ctypes.data, C.POINTER(C.c_size_t)), ng, float(threshold),
+                int(num_results), C.cast(hits.ctypes.data, C.POINTER(BestHit)), cap,
+                C.cast(offs.ctypes.data, C.POINTER(C.c_size_t)), C.byref(bad))
+            if st == _capi.ERR_CAPACITY and int(offs[ng]) > cap:
+                cap = int(offs[ng])
+                continue
+            check(st)
+            break
+        return offs, hits[:int(offs[ng])]
+
+    def search_best(self, queries, group_offsets=None, threshold=0.0, num_results=0, group_size=None):
+        """-> one list per group of BestResult(doc_name, file_no, doc, query, score, positions, ties): for every document
+        the group's best query (see cobs_gpu_search_best)"""
+        offs, hits = self.search_best_arrays(queries, group_offsets, threshold, num_results, group_size)
+        rows = hits.tolist()
+        return [[BestResult(self._names(f)[d], f, d, q, s, p, t) for (f, d, q, s, p, t) in rows[int(offs[g]):int(offs[g + 1])]]
+                for g in range(len(offs) - 1)]
+
+    def best_ms(self):
+        """the last search_best call: best-member and merge kernels, select kernel (HIP events), host ordering;
+        milliseconds -- and how it was launched: device passes, spans that owned their cells, partial states, split groups"""
+        t = (C.c_double * 3)()
+        check(self._lib.cobs_gpu_best_ms(self._h, C.byref(t)))
+        n = (C.c_uint64 * 4)()
+        check(self._lib.cobs_gpu_best_counts(self._h, C.byref(n)))
+        return {"best_ms": t[0], "select_ms": t[1], "order_ms": t[2], "passes": int(n[0]), "own_spans": int(n[1]),
+                "pieces": int(n[2]), "split_groups": int(n[3])}
+
     def positions_ms(self):
         """kernel times of the hit_positions calls since the previous call of this method (HIP events, summed over passes)"""
         t = (C.c_double * 3)()
@@ -1541,7 +1632,7 @@ class Batch:
         return {"scan_ms": a.value, "hash_ms": b.value}
 
 
-__all__ = ["Search", "SearchResult", "GroupResult", "AdjustedResult", "Batch", "CobsGpuError", "unpack_positions", "fpr_adjust"]
+__all__ = ["Search", "SearchResult", "GroupResult", "BestResult", "AdjustedResult", "Batch", "CobsGpuError", "unpack_positions", "fpr_adjust"]
 
 
 class ShardedBatch:

@@ -8,6 +8,7 @@ from cobs_amd import (ClassicIndexParameters, CompactIndexParameters, DocumentEn
 from cobs_amd import AdjustedResult, fpr_adjust  # noqa: F401  (beyond the reference: Search.doc_bits / doc_fill / search_adjusted)
 from cobs_amd import WeightedResult  # noqa: F401  (beyond the reference: Search.search_weighted; shadows no reference name)
 from cobs_amd import GroupResult  # noqa: F401  (beyond the reference: Search.search_groups / search_paired; shadows no reference name)
+from cobs_amd import BestResult  # noqa: F401  (beyond the reference: Search.search_best; shadows no reference name)
 from cobs_amd import SetResult  # noqa: F401  (beyond the reference: Search.set_doc_sets / search_sets; shadows no reference name)
 from cobs_amd import SetQuorumResult  # noqa: F401  (beyond the reference: Search.search_sets_quorum / set_prevalence; shadows no reference name)
 from cobs_amd.construct import (Any, Cortex, Fasta, FastaMulti, Fastq, FastqMulti, KMerBuffer,  # noqa: F401

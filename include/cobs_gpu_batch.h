@@ -152,6 +152,42 @@ cobs_gpu_status cobs_gpu_search_groups(cobs_gpu_index* ix, const char* const* qu
                                        cobs_gpu_group_hit* hits, size_t cap, size_t* hit_offsets /* n_groups + 1 */,
                                        uint64_t* positions /* optional */, size_t* bad_query);
 
+/* ---- best of a group ----------------------------------------------------- */
+/* For every document the BEST query of a group, beyond the reference: typing -- the alleles of a locus, the members of a
+ * gene family are one group, and the question is which of them fits a genome best, and how well.  The other half of the
+ * grouped call (a best member cannot be recovered from a sum).  Group g is the queries [group_offsets[g],
+ * group_offsets[g+1]) of the call, as in cobs_gpu_search_groups.  For query q and file f:
+ *   s(q, d) = the score cobs_gpu_search_batch gives document d (the handle's findere z and invalid-bases policy),
+ *   P(q, f) = the positions that score is out of: T - z under ERROR and MISS, under SKIP the valid positions K1 counts (it
+ *             can be 0; a file with canonicalize == 0 keeps T - z) -- the per-query quantity cobs_gpu_search_groups sums.
+ * Member a is BETTER than member b in document d when, in this order:
+ *   1. s_a * P_b > s_b * P_a: the larger fraction s / P, compared exactly as 64-bit products.  A member with P = 0 has
+ *      s = 0 and the fraction 0: it compares as 0 / 1 (its cross products would otherwise equal everybody's);
+ *   2. s_a > s_b: at equal fraction the longer member, which carries more evidence;
+ *   3. a < b by index in the call.
+ * For every (group, file, real document) the call finds
+ *   query     = the best member, as its index in the call,
+ *   score     = its s,   positions = its P,
+ *   ties      = the number of the group's members whose fraction EQUALS the best one's (s * P_best == s_best * P, P = 0
+ *               taken as 0 / 1), the best one included: two alleles that fit equally well are an ambiguous call.
+ * A document is reported for a group when score >= max(1, ceil(threshold * positions)), the product formed in double;
+ * threshold <= 0 reports every real document of every file, score 0 included.  A group without members reports nothing.
+ * A group's records are ordered by fraction descending (exact cross-multiplication), then score descending, then
+ * (file_no, doc) ascending, cut to the first num_results when num_results > 0; the reference's "max_counts <= 1: index
+ * order" rule does NOT apply; padding slots never appear.  hits[hit_offsets[g] .. hit_offsets[g+1]) belong to group g.
+ * The scores never leave the device: every pass's score rows are merged into the per-(group, document) state of the best
+ * member where they lie; the merge is associative, so a group that is cut by a device pass gives the same records.
+ * Errors as cobs_gpu_search_groups reports them: too short, too long, an invalid base under ERROR (*bad_query = the
+ * offending query) before anything is launched where the host can see it; COBS_GPU_ERR_CAPACITY when cap is too small --
+ * hit_offsets then holds the needed sizes -- or when the state of n_groups x documents does not fit (use fewer groups per
+ * call); COBS_GPU_ERR_ARG for malformed offsets; COBS_GPU_ERR_UNSUPPORTED on a handle opened with an HBM budget or as one
+ * shard of several (and, in the mirrors, on the device list).  cobs_gpu_best_ms (cobs_gpu_diag.h) reads the timers. */
+typedef struct cobs_gpu_best_hit { uint32_t file_no, doc, query, score, positions, ties; } cobs_gpu_best_hit;   /* 24 bytes */
+cobs_gpu_status cobs_gpu_search_best(cobs_gpu_index* ix, const char* const* queries, const size_t* lens, size_t nq,
+                                     const size_t* group_offsets, size_t n_groups, double threshold, size_t num_results,
+                                     cobs_gpu_best_hit* hits, size_t cap, size_t* hit_offsets /* n_groups + 1 */,
+                                     size_t* bad_query);
+
 /* ---- filter fill --------------------------------------------------------- */
 /* How many bits every document's Bloom filter has set, beyond the reference: bits[i] = the rows r in [0, S_p) of the
  * document's sub-index whose bit of score slot slot_begin + i is set (the zero row the engine appends is never counted;

@@ -117,6 +117,15 @@ cobs_gpu_status cobs_gpu_window_ms(cobs_gpu_index* ix, double out[3]);     /* ha
  * over the call's passes), out[1] = the select kernel (HIP events), out[2] = the host's ordering of the records. */
 cobs_gpu_status cobs_gpu_groups_ms(cobs_gpu_index* ix, double out[3]);
 
+/* Durations (ms) of the LAST cobs_gpu_search_best call on this handle: out[0] = the best-member kernel and the merge of
+ * partial states (HIP events, summed over the call's passes), out[1] = the select kernel (HIP events), out[2] = the host's
+ * ordering of the records. */
+cobs_gpu_status cobs_gpu_best_ms(cobs_gpu_index* ix, double out[3]);
+/* How the last cobs_gpu_search_best call was launched: out[0] = device passes, out[1] = (group, pass) spans whose
+ * work-groups owned their cells of the state, out[2] = partial states written by groups whose queries were split over
+ * several work-groups, out[3] = such groups (folds of the merge kernel). */
+cobs_gpu_status cobs_gpu_best_counts(cobs_gpu_index* ix, uint64_t out[4]);
+
 /* The cobs_gpu_doc_bits sweeps of this handle so far (cache hits add nothing): out[0] = milliseconds of the counting
  * kernels (HIP events), out[1] = index bytes they read (rows x valid row bytes), out[2] = milliseconds between HIP events
  * recorded on the copy stream before and after every streamed chunk is brought in (0 on a resident handle) -- the copies

@@ -604,6 +604,41 @@ public:
         }
     }
 
+    //! one document of a group's result: the group's best query in it (its index in the call), that query's score and the
+    //! positions the score is out of, and how many of the group's queries fit equally well (the best one included)
+    struct BestResult {
+        const char* doc_name;
+        uint32_t file_no, doc, query, score, positions, ties;
+    };
+
+    //! every document's best query of a group (beyond the reference; cobs_gpu_search_best): group g is the queries
+    //! [group_offsets[g], group_offsets[g + 1]); results[g] holds the documents whose best query reaches
+    //! max(1, ceil(threshold * its positions)), by score / positions descending, then score, then (file, document)
+    void search_best(const std::vector<std::string>& queries, const std::vector<size_t>& group_offsets,
+                     std::vector<std::vector<BestResult>>& results, double threshold = 0.0, size_t num_results = 0) {
+        if (group_offsets.empty()) throw Error(COBS_GPU_ERR_ARG, "group_offsets needs n_groups + 1 entries");
+        std::vector<const char*> qp;
+        std::vector<size_t> ql;
+        for (const auto& q : queries) { qp.push_back(q.data()); ql.push_back(q.size()); }
+        const size_t ng = group_offsets.size() - 1;
+        std::vector<size_t> offs(ng + 1, 0);
+        std::vector<cobs_gpu_best_hit> hits(16 * ng + 1024);
+        size_t bad = 0;
+        cobs_gpu_status st;
+        for (;;) {
+            st = cobs_gpu_search_best(ix_, qp.data(), ql.data(), queries.size(), group_offsets.data(), ng, threshold, num_results,
+                                      hits.data(), hits.size(), offs.data(), &bad);
+            if (st != COBS_GPU_ERR_CAPACITY || offs[ng] <= hits.size()) break;
+            hits.resize(offs[ng]);          // (the call reported the needed size)
+        }
+        check(st);
+        results.assign(ng, {});
+        for (size_t g = 0; g < ng; ++g)
+            for (size_t i = offs[g]; i < offs[g + 1]; ++i)
+                results[g].push_back(BestResult{cobs_gpu_doc_name(ix_, hits[i].file_no, hits[i].doc), hits[i].file_no, hits[i].doc,
+                                                hits[i].query, hits[i].score, hits[i].positions, hits[i].ties});
+    }
+
     //! the bits set in every document's Bloom filter (beyond the reference; cobs_gpu_doc_bits): one entry per score slot
     //! this handle holds of the file, counted on the device on the first request and cached by the library
     std::vector<uint64_t> doc_bits(size_t file_no = 0) {

@@ -17,7 +17,7 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KERNEL_FILES = ("hash_kernels", "kernels", "scan_findere", "topk_kernels", "build_kernels", "group_kernels", "fill_kernels",
                 "prevalence_kernels", "weighted_kernels", "set_kernels", "set_count_kernels", "coverage_kernels", "window_kernels", "presence_kernels",
-                "fetch_kernels")
+                "fetch_kernels", "best_kernels")
 
 
 def main():
@@ -30,7 +30,8 @@ def main():
     # kernels of the weighted search (weighted_kernels.hip: weights, weighted scan), the document-set kernels
     # (set_kernels.hip: set presence, select; set_count_kernels.hip: set count, quorum select), the coverage scan (coverage_kernels.hip), the window scan
     # (window_kernels.hip), and the other readers of K1's
-    # row-index table (row_table.hpp): the presence kernel and the out-of-core fetch kernels
+    # row-index table (row_table.hpp): the presence kernel and the out-of-core fetch kernels; the best-of-group kernels
+    # (best_kernels.hip: best member, merge of partial states, select, init)
     asm = ""
     for name in KERNEL_FILES:
         src = os.path.join(ROOT, "cobs_amd", "csrc", name + ".hip")
