@@ -211,6 +211,9 @@ SYMBOLS = {
     "cobs_gpu_doc_bits": (_int, [_vp, _sz, C.POINTER(_u64), _sz, C.POINTER(_sz)]),
     "cobs_gpu_doc_bits_ms": (_int, [_vp, C.POINTER(C.c_double * 4)]),
     "cobs_gpu_doc_bits_probe_ms": (_int, [_vp, _sz, C.POINTER(C.c_double)]),
+    "cobs_gpu_doc_shared_bits": (_int, [_vp, _sz, C.POINTER(_u32), _sz, _pu64, _pu64, _sz, C.POINTER(_sz)]),
+    "cobs_gpu_jaccard_estimate": (_int, [_u64, _u32, _u64, _u64, _u64, C.POINTER(C.c_double * 5)]),
+    "cobs_gpu_similarity_ms": (_int, [_vp, C.POINTER(C.c_double * 4)]),
     "cobs_gpu_batch_create": (_int, [_vp, _sz, _sz, C.POINTER(_vp)]),
     "cobs_gpu_batch_destroy": (None, [_vp]),
     "cobs_gpu_batch_set_queries": (_int, [_vp, C.POINTER(_cp), C.POINTER(_sz), _sz]),

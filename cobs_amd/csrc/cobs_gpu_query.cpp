@@ -35,6 +35,13 @@ static void usage() {
                  "[-d DEVICE[,DEVICE...]] [--hbm-budget GIB] [--findere Z] [--invalid-bases MODE] [--positions] [--prevalence] [--weighted] [--coverage] [--window N] [--fpr-adjust] [--sets FILE.tsv [--sets-by any|all | --sets-quorum X | --sets-profile]] (QUERY | -f QUERY_FILE)\n"
                  "       cobs_gpu_query doc-stats INDEX [--fill-above X]\n"
                  "         one line per document: file, name, sub-index, S_p, bits set in its filter, fill = bits / S_p, fpr = fill^H\n"
+                 "       cobs_gpu_query doc-similarity INDEX --like NAME[,NAME...] [--min-jaccard J] [-l N]\n"
+                 "       cobs_gpu_query doc-similarity INDEX --all-pairs --min-jaccard J\n"
+                 "         the documents that share filter bits, by the Bloom-filter estimate of the Jaccard index of their k-mer sets;\n"
+                 "         one line per pair: ref, doc, sub-index, shared bits, bit_jaccard, jaccard, containment_ref_in_doc,\n"
+                 "         containment_doc_in_ref.  --like: per named document the others of ITS sub-index, best first (-l N: the\n"
+                 "         first N); --all-pairs: every pair a < b of one sub-index whose estimate reaches J, in (a, b) order.\n"
+                 "         Documents of different sub-indexes of a compact index are never compared.\n"
                  "       --fpr-adjust: every result line gets expected_fp (the positions the document's fill alone is expected to\n"
                  "         hit) and adjusted (the estimate of the truly shared positions) appended\n"
                  "       [--group N|all] [--read-threshold X]\n"
@@ -482,6 +489,98 @@ static int doc_stats(int argc, char** argv) {
     return 0;
 }
 
+// `doc-similarity INDEX (--like NAME[,NAME...] [--min-jaccard J] [-l N] | --all-pairs --min-jaccard J)`: one line per pair,
+//   ref  doc  sub_index  shared  bit_jaccard  jaccard  containment_ref_in_doc  containment_doc_in_ref
+// (the floats with 17 significant digits, so that they read back as computed; a saturated filter's estimates are nan)
+static void similarity_line(const char* ref, const cobs_gpu::ClassicSearch::SimilarDocument& r) {
+    auto num = [](double v) {
+        char buf[40];
+        if (std::isnan(v)) return std::string("nan");
+        std::snprintf(buf, sizeof buf, "%.17g", v);
+        return std::string(buf);
+    };
+    std::printf("%s\t%s\t%u\t%llu\t%s\t%s\t%s\t%s\n", ref, r.doc_name, r.sub_index, (unsigned long long)r.shared, num(r.bit_jaccard).c_str(),
+                num(r.jaccard).c_str(), num(r.containment_ref_in_doc).c_str(), num(r.containment_doc_in_ref).c_str());
+}
+
+static int doc_similarity(int argc, char** argv) {
+    std::string path, like;
+    bool all_pairs = false, have_min = false, have_limit = false;
+    double min_jaccard = 0.0;
+    size_t limit = 0;
+    for (int i = 2; i < argc; ++i) {
+        const std::string a = argv[i];
+        if (a == "--like" && i + 1 < argc) like = argv[++i];
+        else if (a == "--min-jaccard" && i + 1 < argc) { min_jaccard = std::atof(argv[++i]); have_min = true; }
+        else if ((a == "-l" || a == "--limit") && i + 1 < argc) { limit = (size_t)std::strtoull(argv[++i], nullptr, 10); have_limit = true; }
+        else if (a == "--all-pairs") all_pairs = true;
+        else if (!a.empty() && a[0] != '-' && path.empty()) path = a;
+        else { usage(); return 1; }
+    }
+    if (path.empty() || all_pairs == !like.empty()) { usage(); return 1; }
+    if (all_pairs && !have_min) {
+        std::fprintf(stderr, "doc-similarity --all-pairs needs --min-jaccard J: the list of all pairs grows with the square of the documents\n");
+        return 1;
+    }
+    if (all_pairs && have_limit) {
+        std::fprintf(stderr, "doc-similarity: -l cuts the list of one --like reference, not --all-pairs\n");
+        return 1;
+    }
+    try {
+        cobs_gpu::ClassicSearch s(path);
+        cobs_gpu_index_info info;
+        if (cobs_gpu_info(s.handle(), 0, &info) != COBS_GPU_OK) throw cobs_gpu::Error(COBS_GPU_ERR_ARG, cobs_gpu_last_error());
+        if (!all_pairs) {
+            std::unordered_map<std::string, uint32_t> doc_of;
+            for (uint64_t d = info.num_docs; d-- > 0;) doc_of[cobs_gpu_doc_name(s.handle(), 0, d)] = (uint32_t)d;    // (the first of equal names)
+            std::vector<uint32_t> refs;
+            for (size_t at = 0; at <= like.size();) {
+                const size_t end = std::min(like.find(',', at), like.size());
+                const std::string name = like.substr(at, end - at);
+                const auto it = doc_of.find(name);
+                if (it == doc_of.end()) {
+                    std::fprintf(stderr, "doc-similarity: no document named %s in %s\n", name.c_str(), path.c_str());
+                    return 1;
+                }
+                refs.push_back(it->second);
+                at = end + 1;
+            }
+            const auto lists = s.similar_documents(refs, 0, min_jaccard, limit);
+            for (size_t i = 0; i < refs.size(); ++i)
+                for (const auto& r : lists[i]) similarity_line(cobs_gpu_doc_name(s.handle(), 0, refs[i]), r);
+            return 0;
+        }
+        // every pair a < b of one sub-index, sub-index by sub-index: kChunk references per call (the library sweeps them panel
+        // by panel), so the host holds kChunk rows of cells at a time and never a D x D buffer
+        constexpr uint64_t kChunk = 64;
+        const std::vector<uint64_t> bits = s.doc_bits(0);
+        const uint64_t per = info.kind == 0 ? info.counts_size : 8 * info.page_size;
+        for (uint64_t d0 = 0, pg = 0; d0 < info.num_docs; d0 += per, ++pg) {
+            const uint64_t live = std::min<uint64_t>(per, info.num_docs - d0), sig = cobs_gpu_signature_size(s.handle(), 0, (uint32_t)pg);
+            for (uint64_t a0 = 0; a0 + 1 < live; a0 += kChunk) {
+                std::vector<uint32_t> refs;
+                for (uint64_t a = a0; a < std::min(a0 + kChunk, live - 1); ++a) refs.push_back((uint32_t)(d0 + a));
+                const auto shared = s.doc_shared_bits(refs, 0);
+                for (size_t i = 0; i < refs.size(); ++i) {
+                    const uint64_t a = refs[i];
+                    for (uint64_t b = a + 1; b < d0 + live; ++b) {
+                        const uint64_t c = shared[i][b - d0];
+                        const auto e = cobs_gpu::ClassicSearch::jaccard_estimate(sig, (uint32_t)info.num_hashes, bits[a], bits[b], c);
+                        if (!cobs_gpu::ClassicSearch::reaches(e.jaccard, min_jaccard)) continue;
+                        similarity_line(cobs_gpu_doc_name(s.handle(), 0, a),
+                                        cobs_gpu::ClassicSearch::SimilarDocument{cobs_gpu_doc_name(s.handle(), 0, b), b, (uint32_t)pg, c, e.bit_jaccard,
+                                                                                 e.jaccard, e.containment_a_in_b, e.containment_b_in_a});
+                    }
+                }
+            }
+        }
+    } catch (const cobs_gpu::Error& e) {
+        std::fprintf(stderr, "EXCEPTION: %s\n", e.what());
+        return 1;
+    }
+    return 0;
+}
+
 int cobs_gpu_tools_main(int argc, char** argv);      // cobs_gpu_tools.cpp: *-construct, classic-combine, compact-construct-combine
 
 int main(int argc, char** argv) {
@@ -490,6 +589,7 @@ int main(int argc, char** argv) {
         if (rc >= 0) return rc;
         if (argc > 1 && std::string(argv[1]) == "query") { ++argv; --argc; }       // `cobs query ...`
         if (argc > 1 && std::string(argv[1]) == "doc-stats") return doc_stats(argc, argv);
+        if (argc > 1 && std::string(argv[1]) == "doc-similarity") return doc_similarity(argc, argv);
     }
     // `cobs benchmark-fpr IN_FILE [-k N] [-q N] [-w N] [-d|--dist] [--seed S]` (src/cobs.cpp:672-730): the index is the
     // positional argument and -d means --dist, as there; the device list of this tool is spelled --device in this mode

@@ -168,6 +168,7 @@ cobs_gpu_index::~cobs_gpu_index() {
     if (coverage) destroy_coverage_work(coverage);
     if (window) destroy_window_work(window);
     if (best) destroy_best_work(best);
+    if (similarity) destroy_similarity_work(similarity);
     for (auto* b : scratch) delete b;
     if (xchg_stream) (void)hipStreamDestroy(xchg_stream);
 }

@@ -313,6 +313,7 @@ struct SetsWork;        // sets.cpp: labels, segment records and bitmaps of cobs
 struct CoverageWork;    // coverage.cpp: thresholds and hit pool of cobs_gpu_search_coverage
 struct WindowWork;      // window.cpp: thresholds, windows and hit pool of cobs_gpu_search_window
 struct BestWork;        // best.cpp: scratch batches, best-member state and pool of cobs_gpu_search_best
+struct SimilarityWork;  // similarity.cpp: reference bytes, cells and timers of cobs_gpu_doc_shared_bits
 
 }  // namespace cobs_amd
 
@@ -343,6 +344,7 @@ struct cobs_gpu_index {
     cobs_amd::CoverageWork* coverage = nullptr;     // coverage.cpp
     cobs_amd::WindowWork* window = nullptr;         // window.cpp
     cobs_amd::BestWork* best = nullptr;             // best.cpp
+    cobs_amd::SimilarityWork* similarity = nullptr; // similarity.cpp
     ~cobs_gpu_index();
 };
 
@@ -603,6 +605,7 @@ void destroy_sets_work(SetsWork* w);               // sets.cpp
 void destroy_coverage_work(CoverageWork* w);       // coverage.cpp
 void destroy_window_work(WindowWork* w);           // window.cpp
 void destroy_best_work(BestWork* w);               // best.cpp
+void destroy_similarity_work(SimilarityWork* w);   // similarity.cpp
 void drop_fill_cache(cobs_gpu_index* ix, size_t file_no);   // ... the cached counts of one file (its bits changed)
 bool rank_on_device_applies(const cobs_gpu_batch* b, size_t nq);
 cobs_gpu_status rank_launch(cobs_gpu_batch* b, size_t q_first, size_t nq, size_t limit);

@@ -261,6 +261,16 @@ def covered_bases(words, n, span):
     return int(_capi.load().cobs_gpu_covered_bases(C.cast(w.ctypes.data, C.POINTER(C.c_uint64)), n, int(span)))
 
 
+def jaccard_estimate(sig, num_hashes, bits_a, bits_b, shared_ab):
+    """cobs_gpu_jaccard_estimate -> (bit_jaccard, jaccard, containment_a_in_b, containment_b_in_a, n_inter): the
+    Bloom-filter estimate of two documents' k-mer set similarity from their set bits (Search.doc_bits), their shared bits
+    (Search.doc_shared_bits) and their sub-index's signature size and hash count.  Host arithmetic, no device; the three
+    estimates and n_inter are NaN when the union of the two filters is saturated."""
+    out = (C.c_double * 5)()
+    check(_capi.load().cobs_gpu_jaccard_estimate(int(sig), int(num_hashes), int(bits_a), int(bits_b), int(shared_ab), C.byref(out)))
+    return tuple(float(v) for v in out)
+
+
 def best_window(bits_or_words, n, window):
     """cobs_gpu_best_window -> (best, start): the largest number of set positions in any min(window, n) consecutive
     positions of one hit (its Search.hit_positions words, or a bool vector of at least n positions), and the smallest
@@ -517,6 +527,72 @@ class Search:
         t = (C.c_double * 4)()
         check(self._lib.cobs_gpu_doc_bits_ms(self._h, C.byref(t)))
         return {"kernel_ms": t[0], "bytes_read": int(t[1]), "pcie_ms": t[2], "passes": int(t[3])}
+
+    # -- document similarity: shared filter bits ---------------------------------
+    def doc_shared_bits(self, refs, file_no=0):
+        """cobs_gpu_doc_shared_bits: for every reference document refs[i] of the file, in how many rows it and every
+        document of ITS sub-index both have their bit set -> list of uint64 arrays, one per reference, one entry per
+        score slot of that sub-index in slot order (classic: counts_size entries; compact: 8 * page_size; entry of the
+        reference itself = its doc_bits).  Documents of different sub-indexes are not comparable and never paired."""
+        r = np.ascontiguousarray(refs, dtype=np.uint32).reshape(-1)
+        n = len(r)
+        offs = np.zeros(n + 1, dtype=np.uint64)
+        need = C.c_size_t(0)
+        rp, op = r.ctypes.data_as(C.POINTER(C.c_uint32)), offs.ctypes.data_as(C.POINTER(C.c_uint64))
+        check(self._lib.cobs_gpu_doc_shared_bits(self._h, int(file_no), rp, n, op, None, 0, C.byref(need)))
+        out = np.zeros(need.value, dtype=np.uint64)
+        check(self._lib.cobs_gpu_doc_shared_bits(self._h, int(file_no), rp, n, op, out.ctypes.data_as(C.POINTER(C.c_uint64)), out.size,
+                                                 C.byref(need)))
+        return [out[int(offs[i]):int(offs[i + 1])] for i in range(n)]
+
+    def similarity_ms(self):
+        """the doc_shared_bits panels of this handle since the last read (reset by the read): extraction ms, sweep ms,
+        index bytes the sweeps read, sweeps"""
+        t = (C.c_double * 4)()
+        check(self._lib.cobs_gpu_similarity_ms(self._h, C.byref(t)))
+        return {"extract_ms": t[0], "sweep_ms": t[1], "bytes_read": int(t[2]), "sweeps": int(t[3])}
+
+    def _sub_index_of(self, file_no, doc):
+        """-> (sub-index, its first document, S_p) of a real document"""
+        i = self.info(file_no)
+        per = int(i.counts_size) if int(i.kind) == 0 else 8 * int(i.page_size)
+        pg = int(doc) // per
+        return pg, pg * per, self.signature_size(file_no, pg)
+
+    def similar_documents(self, ref, file_no=0, min_jaccard=0.0, num_results=0):
+        """the real documents of ref's sub-index other than ref itself, by the Bloom-filter estimate of the Jaccard index of
+        their k-mer sets (jaccard_estimate over doc_bits and doc_shared_bits) -> list of (doc_name, jaccard,
+        containment_ref_in_doc, containment_doc_in_ref, shared), estimated Jaccard descending, then document index; documents
+        whose estimate is NaN (a saturated filter) follow every finite one, ordered by bit_jaccard descending.  min_jaccard
+        <= 0 is no threshold; a positive one keeps the documents whose ESTIMATE reaches it, so a NaN estimate passes no
+        threshold (the one rule, also of `cobs_gpu_query doc-similarity`); num_results > 0 cuts the list.  ref is a document
+        index or name."""
+        names = self._names(file_no)
+        if isinstance(ref, (str, bytes)):
+            name = ref.decode() if isinstance(ref, bytes) else ref
+            if name not in names:
+                raise KeyError("no document named %r" % name)
+            ref = names.index(name)
+        ref = int(ref)
+        if not 0 <= ref < len(names):
+            raise CobsGpuError(_capi.ERR_ARG, "similar_documents: reference %d is not a document of the file" % ref)
+        shared = self.doc_shared_bits([ref], file_no)[0]
+        bits = self._real_doc_bits(file_no)
+        _pg, d0, sig = self._sub_index_of(file_no, ref)
+        H = int(self.info(file_no).num_hashes)
+        rows = []
+        for s in range(min(len(shared), len(names) - d0)):
+            d = d0 + s
+            if d == ref:
+                continue
+            bj, j, c_ab, c_ba, _n = jaccard_estimate(sig, H, int(bits[ref]), int(bits[d]), int(shared[s]))
+            nan = j != j
+            if min_jaccard > 0 and not j >= min_jaccard:
+                continue
+            rows.append(((nan, -(bj if nan else j), d), (names[d], j, c_ab, c_ba, int(shared[s]))))
+        rows.sort(key=lambda t: t[0])
+        out = [r for _k, r in rows]
+        return out[:num_results] if num_results and num_results > 0 else out
 
     def search_adjusted(self, query, threshold=0.0, num_results=0):
         """search() whose results also carry expected_fp and adjusted (fpr_adjust over the document's fill, the handle's
@@ -1463,6 +1539,13 @@ class MultiSearch(Search):
     def doc_bits(self, file_no=0):
         """refused: a document's filter lives on one rank (doc_fill, doc_fpr and search_adjusted follow)"""
         raise CobsGpuError(_capi.ERR_UNSUPPORTED, "doc_bits: not on a device-list handle (ask the shards: shard(rank).doc_bits)")
+
+    def doc_shared_bits(self, refs, file_no=0):
+        """refused: a sub-index's columns may be cut between the ranks (similar_documents follows)"""
+        raise CobsGpuError(_capi.ERR_UNSUPPORTED, "doc_shared_bits: not on a device-list handle")
+
+    def similar_documents(self, ref, file_no=0, min_jaccard=0.0, num_results=0):
+        raise CobsGpuError(_capi.ERR_UNSUPPORTED, "similar_documents: not on a device-list handle")
 
 
 class _DevArray:

@@ -203,6 +203,38 @@ cobs_gpu_status cobs_gpu_search_best(cobs_gpu_index* ix, const char* const* quer
  * counterpart: ask the shards (cobs_gpu_multi_index). */
 cobs_gpu_status cobs_gpu_doc_bits(cobs_gpu_index* ix, size_t file_no, uint64_t* bits, size_t cap, size_t* needed);
 
+/* ---- document similarity ------------------------------------------------- */
+/* Shared filter bits of documents, beyond the reference.  For documents a and b of the SAME sub-index p of file f,
+ *   shared(f, a, b) = the rows r in [0, S_p) in which both have their bit set;   shared(f, a, a) = cobs_gpu_doc_bits' value.
+ * A classic index is one sub-index; the sub-index of document d of a compact index is d / (8 * page_size).  Documents of
+ * different sub-indexes have different S_p and are not comparable: the call never pairs them.
+ * For every reference refs[i] (a real document of file_no; references may repeat, come in any order and lie in different
+ * sub-indexes) the cells shared[offsets[i] .. offsets[i+1]) receive shared(file_no, refs[i], d) for every score slot d of
+ * refs[i]'s sub-index, in slot order: 8 * page_size cells for a compact index, counts_size for a classic one; a padding
+ * slot is counted like any other column and is 0 in a well-formed file.  offsets (n_refs + 1 entries) is filled whenever
+ * it is not NULL and *needed (optional) is set to offsets[n_refs], also by a call that fails with COBS_GPU_ERR_CAPACITY
+ * (shared is NULL or cap is too small; shared is not written).  shared == NULL with cap == 0 is the sizing call and
+ * succeeds.  n_refs == 0 succeeds with *needed = 0.
+ * On the device the references of one sub-index are taken in panels of 8, in ascending document order: a panel is one
+ * pass that extracts the references' bits of every row and one sweep over the sub-index's rows, so a call makes
+ * sum over sub-indexes of ceil(its references / 8) sweeps (cobs_gpu_similarity_ms, cobs_gpu_diag.h).  Nothing is cached.
+ * Everything the host can refuse is refused before any device work: COBS_GPU_ERR_ARG (NULL handle, NULL refs, file_no out
+ * of range, a reference >= the file's num_docs), COBS_GPU_ERR_UNSUPPORTED on a handle opened with an HBM budget or as one
+ * shard of several (its rows or columns are not all resident).  The device list (cobs_gpu_multi_*) has no counterpart. */
+cobs_gpu_status cobs_gpu_doc_shared_bits(cobs_gpu_index* ix, size_t file_no, const uint32_t* refs, size_t n_refs,
+                                         uint64_t* offsets /* n_refs + 1 */, uint64_t* shared, size_t cap, size_t* needed);
+/* The Bloom-filter estimate of the Jaccard index and the containment of two documents' k-mer sets from their fills and
+ * their shared bits (host arithmetic, no device): out = {bit_jaccard, jaccard, containment_a_in_b, containment_b_in_a,
+ * n_inter}.  All in double, with t_or = bits_a + bits_b - shared_ab and n(t) = -(sig / num_hashes) * log1p(-t / sig):
+ *   n_inter = max(0, n(bits_a) + n(bits_b) - n(t_or)),   jaccard = n_inter / n(t_or),
+ *   containment_a_in_b = min(1, n_inter / n(bits_a)),   containment_b_in_a = min(1, n_inter / n(bits_b)),
+ *   bit_jaccard = shared_ab / t_or;   a zero denominator gives 0.
+ * t_or == sig (a saturated filter): the three estimates and n_inter are NaN, bit_jaccard still answers.
+ * COBS_GPU_ERR_ARG: sig == 0, num_hashes == 0, shared_ab > min(bits_a, bits_b), bits_a or bits_b > sig, t_or > sig (no
+ * two columns of one sub-index give that), out == NULL. */
+cobs_gpu_status cobs_gpu_jaccard_estimate(uint64_t sig, uint32_t num_hashes, uint64_t bits_a, uint64_t bits_b, uint64_t shared_ab,
+                                          double out[5]);
+
 /* ---- query prevalence ---------------------------------------------------- */
 /* For every position of a query, HOW MANY documents hold it, beyond the reference: the profile along the query (a
  * conservation track of a gene, the core and accessory stretches of a contig, the ubiquitous k-mers that inflate every

@@ -136,6 +136,12 @@ cobs_gpu_status cobs_gpu_doc_bits_ms(cobs_gpu_index* ix, double out[4]);
  * load and one store per lane; *ms = HIP-event milliseconds of one such sweep (scripts/probes/fill_probe.py). */
 cobs_gpu_status cobs_gpu_doc_bits_probe_ms(cobs_gpu_index* ix, size_t file_no, double* ms);
 
+/* The cobs_gpu_doc_shared_bits panels of this handle since the last read (the figures are reset by this call): out[0] =
+ * milliseconds of the kernels that extract the references' bits of every row, out[1] = milliseconds of the sweeps (the
+ * zeroing of the cells and the counting kernel), both between HIP events, out[2] = index bytes the sweeps read (rows x
+ * valid row bytes), out[3] = sweeps (one per panel of up to 8 references of one sub-index). */
+cobs_gpu_status cobs_gpu_similarity_ms(cobs_gpu_index* ix, double out[4]);
+
 /* Diagnostics of tuning builds (libcobs_gpu_timing.so, `make -C cobs_amd/csrc timing`): s_memtime stamps
  * [work-group slot][wave 0..3][8 phases] of the work-groups sampled from the last scan launch after
  * cobs_gpu_set_tuning(ix, "phase_slots", n).  The production library records nothing (*n_words = 0). */

@@ -660,6 +660,82 @@ public:
         return fill;
     }
 
+    //! document similarity (beyond the reference; cobs_gpu_doc_shared_bits): for every reference document refs[i] of the
+    //! file, in how many rows it and every document of ITS sub-index both have their bit set -- one vector per reference,
+    //! one entry per score slot of that sub-index in slot order (classic: counts_size entries; compact: 8 * page_size;
+    //! the reference's own entry = its doc_bits).  Documents of different sub-indexes are not comparable and never paired.
+    std::vector<std::vector<uint64_t>> doc_shared_bits(const std::vector<uint32_t>& refs, size_t file_no = 0) {
+        std::vector<uint64_t> offs(refs.size() + 1, 0);
+        size_t need = 0;
+        check(cobs_gpu_doc_shared_bits(ix_, file_no, refs.data(), refs.size(), offs.data(), nullptr, 0, &need));
+        std::vector<uint64_t> cells(need);
+        check(cobs_gpu_doc_shared_bits(ix_, file_no, refs.data(), refs.size(), offs.data(), cells.data(), cells.size(), &need));
+        std::vector<std::vector<uint64_t>> out(refs.size());
+        for (size_t i = 0; i < refs.size(); ++i) out[i].assign(cells.begin() + offs[i], cells.begin() + offs[i + 1]);
+        return out;
+    }
+
+    //! the Bloom-filter estimate of two documents' k-mer set similarity (cobs_gpu_jaccard_estimate, host arithmetic); the
+    //! three estimates and n_inter are NaN when the union of the two filters is saturated, bit_jaccard still answers
+    struct JaccardEstimate {
+        double bit_jaccard = 0, jaccard = 0, containment_a_in_b = 0, containment_b_in_a = 0, n_inter = 0;
+    };
+    static JaccardEstimate jaccard_estimate(uint64_t sig, uint32_t num_hashes, uint64_t bits_a, uint64_t bits_b, uint64_t shared_ab) {
+        double v[5];
+        check(cobs_gpu_jaccard_estimate(sig, num_hashes, bits_a, bits_b, shared_ab, v));
+        JaccardEstimate e;
+        e.bit_jaccard = v[0], e.jaccard = v[1], e.containment_a_in_b = v[2], e.containment_b_in_a = v[3], e.n_inter = v[4];
+        return e;
+    }
+    //! the one rule of a Jaccard threshold: min_jaccard <= 0 is no threshold and keeps every pair; a positive one keeps
+    //! the pairs whose ESTIMATE reaches it, so a NaN estimate (a saturated filter) passes no threshold
+    static bool reaches(double jaccard, double min_jaccard) { return !(min_jaccard > 0.0) || jaccard >= min_jaccard; }
+
+    struct SimilarDocument {
+        const char* doc_name;
+        uint64_t doc;           // document index in the file
+        uint32_t sub_index;
+        uint64_t shared;
+        double bit_jaccard, jaccard, containment_ref_in_doc, containment_doc_in_ref;
+    };
+    //! per reference the real documents of its sub-index other than itself, estimated Jaccard descending, then document
+    //! index; documents whose estimate is NaN follow every finite one, ordered by bit_jaccard descending.  min_jaccard:
+    //! see reaches(); num_results > 0 cuts each list.  All references go through ONE doc_shared_bits call.
+    std::vector<std::vector<SimilarDocument>> similar_documents(const std::vector<uint32_t>& refs, size_t file_no = 0,
+                                                                double min_jaccard = 0.0, size_t num_results = 0) {
+        const cobs_gpu_index_info info = whole_file_info(file_no);
+        for (uint32_t r : refs)
+            if (r >= info.num_docs) throw Error(COBS_GPU_ERR_ARG, "similar_documents: a reference that is not a document of the file");
+        const std::vector<std::vector<uint64_t>> shared = doc_shared_bits(refs, file_no);
+        const std::vector<uint64_t> bits = doc_bits(file_no);
+        const uint64_t per = info.kind == 0 ? info.counts_size : 8 * info.page_size;
+        std::vector<std::vector<SimilarDocument>> out(refs.size());
+        for (size_t i = 0; i < refs.size(); ++i) {
+            const uint64_t ref = refs[i];
+            const uint32_t pg = page_of(info, ref);
+            const uint64_t d0 = info.kind == 0 ? 0 : pg * per, sig = cobs_gpu_signature_size(ix_, file_no, pg);
+            std::vector<SimilarDocument>& rows = out[i];
+            for (uint64_t s = 0; s < shared[i].size() && d0 + s < info.num_docs; ++s) {
+                const uint64_t d = d0 + s;
+                if (d == ref) continue;
+                const JaccardEstimate e = jaccard_estimate(sig, (uint32_t)info.num_hashes, bits[ref], bits[d], shared[i][s]);
+                if (!reaches(e.jaccard, min_jaccard)) continue;
+                rows.push_back(SimilarDocument{cobs_gpu_doc_name(ix_, file_no, d), d, pg, shared[i][s], e.bit_jaccard, e.jaccard,
+                                               e.containment_a_in_b, e.containment_b_in_a});
+            }
+            std::stable_sort(rows.begin(), rows.end(), [](const SimilarDocument& a, const SimilarDocument& b) {
+                const bool na = std::isnan(a.jaccard), nb = std::isnan(b.jaccard);
+                if (na != nb) return nb;
+                return na ? a.bit_jaccard > b.bit_jaccard : a.jaccard > b.jaccard;
+            });
+            if (num_results > 0 && rows.size() > num_results) rows.resize(num_results);
+        }
+        return out;
+    }
+    std::vector<SimilarDocument> similar_documents(uint32_t ref, size_t file_no = 0, double min_jaccard = 0.0, size_t num_results = 0) {
+        return similar_documents(std::vector<uint32_t>{ref}, file_no, min_jaccard, num_results)[0];
+    }
+
     //! what a score is worth: expected_fp = the positions the document's filter fill alone is expected to hit, adjusted =
     //! the method-of-moments estimate of the positions that are truly shared (cobs_gpu_batch.h, "filter fill")
     struct Adjusted {
