@@ -758,6 +758,7 @@ cobs_gpu_status cobs_gpu_read_rows(const cobs_gpu_index* ix, size_t f, uint32_t 
 
 uint64_t cobs_gpu_graph_replays(const cobs_gpu_index* ix) { return ix ? ix->graph_replays : 0; }
 uint64_t cobs_gpu_host_passes(const cobs_gpu_index* ix) { return ix ? ix->host_passes : 0; }
+uint64_t cobs_gpu_self_hash_passes(const cobs_gpu_index* ix) { return ix ? ix->self_hash_passes : 0; }
 
 // True positives for the procedural index: see include/cobs_gpu_batch.h.
 cobs_gpu_status cobs_gpu_plant(cobs_gpu_index* ix, size_t f, const char* text, size_t len, const uint32_t* docs,

@@ -332,6 +332,7 @@ struct cobs_gpu_index {
     cobs_amd::ResultArena arena;  // cobs_gpu_search_batch_view
     uint64_t host_passes = 0;     // device passes launched by the host-buffer calls
     uint64_t graph_replays = 0;   // small passes of the host API served by a captured hipGraph
+    uint64_t self_hash_passes = 0;   // passes that ran in the self-hashing form (pass_self_hash), replays of such a graph included
     static constexpr int kScratch = 3;
     cobs_gpu_batch* scratch[kScratch] = {nullptr, nullptr, nullptr};   // workspaces of the host-buffer search API
     hipStream_t xchg_stream = nullptr;   // sharded search: the stream the ranks' agreements and exchanges of its passes run on (sharded.cpp)
@@ -439,6 +440,8 @@ struct cobs_gpu_batch {
     cobs_amd::PinnedBuf<uint8_t> h_res;
     size_t res_topk = 0, res_pool = 0, res_pool_n = 0;
     bool res_rows = false;            // ... and the score rows of an all-documents pass, into h_rows
+    bool self_hash_run = false;       // the last run_impl took the self-hashing form
+    bool graph_self_hash = false;     // ... and so did the run the current graph was captured from (diagnostics)
     // shapes captured earlier (a service sees a handful of read lengths, not one): the current graph
     // above plus a few older ones, least recently used first to go; and the keys of shapes seen once
     // (the second sighting of a shape captures it, whatever ran in between)
@@ -447,6 +450,7 @@ struct cobs_gpu_batch {
         uint64_t key = 0, used = 0;
         size_t res_topk = 0, res_pool = 0, res_pool_n = 0;
         bool res_rows = false;
+        bool self_hash = false;
     };
     GraphEntry graph_more[3];
     uint64_t graph_recent[4] = {0, 0, 0, 0};

@@ -95,6 +95,7 @@ static cobs_gpu_status host_pass_begin(cobs_gpu_index* ix, int slot, const char*
                 std::swap(e.res_pool, b->res_pool);
                 std::swap(e.res_pool_n, b->res_pool_n);
                 std::swap(e.res_rows, b->res_rows);
+                std::swap(e.self_hash, b->graph_self_hash);
                 e.used = ++b->graph_clock;
                 break;
             }
@@ -117,6 +118,7 @@ static cobs_gpu_status host_pass_begin(cobs_gpu_index* ix, int slot, const char*
             b->read_seq = b->run_seq;        // no events of this run: cobs_gpu_batch_kernel_ms starts behind it
             b->ran = true;
             ix->graph_replays++;
+            if (b->graph_self_hash) ix->self_hash_passes++;      // the pass the graph was captured from ran without K1
             HIP_TRY(hipEventRecord(b->done, b->own_stream));
             return COBS_GPU_OK;
         }
@@ -172,6 +174,7 @@ static cobs_gpu_status host_pass_begin(cobs_gpu_index* ix, int slot, const char*
                         lru->res_pool = b->res_pool;
                         lru->res_pool_n = b->res_pool_n;
                         lru->res_rows = b->res_rows;
+                        lru->self_hash = b->graph_self_hash;
                         lru->used = ++b->graph_clock;
                     }
                     b->graph_exec = exec;
@@ -184,6 +187,7 @@ static cobs_gpu_status host_pass_begin(cobs_gpu_index* ix, int slot, const char*
                     b->res_pool = res_pool;
                     b->res_pool_n = pool_n;
                     b->res_rows = row_bytes_all != 0;
+                    b->graph_self_hash = b->self_hash_run;
                     (void)hipGraphDestroy(graph);
                     if (!b->graph_t0) {
                         HIP_TRY(hipEventCreate(&b->graph_t0));

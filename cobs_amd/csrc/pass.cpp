@@ -364,6 +364,8 @@ cobs_gpu_status cobs_amd::run_impl(cobs_gpu_batch* b, double threshold, size_t t
     const bool count_valid = b->invalid_bases != COBS_GPU_INVALID_ERROR && nq;
     // the self-hashing shape class (tuning key scan_self_hash): this pass launches no K1 and reads no table
     const bool self_hash = pass_self_hash(b, threshold);
+    b->self_hash_run = self_hash;
+    if (self_hash) ix->self_hash_passes++;        // (diagnostics: cobs_gpu_self_hash_passes)
     // invalid_bases = skip: a file's thresholds follow the content of the queries -- made on the device right behind its K1
     // (no host staging: a replayed graph serves other text of its shape class)
     const bool skip_thr = need_thr && b->invalid_bases == COBS_GPU_INVALID_SKIP;

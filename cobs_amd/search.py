@@ -1439,6 +1439,11 @@ class Search:
         """device passes the host-buffer calls have launched on this handle so far"""
         return int(self._lib.cobs_gpu_host_passes(self._h))
 
+    @property
+    def self_hash_passes(self):
+        """passes on this handle so far that ran in the self-hashing form of the scan (no K1), graph replays included"""
+        return int(self._lib.cobs_gpu_self_hash_passes(self._h))
+
     def stream_counters(self):
         """out-of-core handles: (chunks fetched row by row, chunks copied whole) over all passes so far"""
         c = (C.c_uint64 * 2)()

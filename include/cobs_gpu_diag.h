@@ -156,6 +156,12 @@ uint64_t cobs_gpu_graph_replays(const cobs_gpu_index* ix);
  * handle so far, replays included: a call is cut into passes (cobs_gpu.h), and a call that came back with
  * COBS_GPU_ERR_CAPACITY and was made again has paid for its passes twice -- the view call grows its arena instead. */
 uint64_t cobs_gpu_host_passes(const cobs_gpu_index* ix);
+/* Passes on this handle so far that ran in the self-hashing form of the scan (tuning key "scan_self_hash": no K1 launch,
+ * the scan work-groups hash their query's terms themselves), whichever call drove them: the host-buffer calls, the view
+ * call, cobs_gpu_search_groups, cobs_gpu_search_best and the runs of a caller's own batches on the handle.  A replay of a
+ * graph that was captured from such a pass counts too, as in cobs_gpu_graph_replays.  Says which form a call took where no
+ * batch of the caller's is at hand to ask (cobs_gpu_batch_stats: table_bytes). */
+uint64_t cobs_gpu_self_hash_passes(const cobs_gpu_index* ix);
 
 /* Out-of-core handles (hbm_budget_bytes): how the chunks of all passes so far were brought into HBM.
  * out[0] = chunks whose looked-up rows were fetched one by one from the registered file mapping (a batch that

@@ -7,7 +7,9 @@ ordered pair (A directly followed by B, A by A) occurs.  Into the circuit go the
 every family F one failing call of ANOTHER family is put behind an occurrence of F and followed by a regular step of F
 (the circuit's pairs stay as they are: ... F, failing X, F, next ...).  Between the steps findere z, the invalid-bases
 policy, pass_bytes, graph, the query count and the query lengths change on a seeded schedule (COBS_FUZZ_SEED shifts it) in
-which every family meets every value; the labels of the document sets go through five states in time order.
+which every family meets every value; the labels of the document sets go through five states in time order.  The
+self-hashing scan (tuning key scan_self_hash: 0 or 2) is one of those settings: must_self_hash / never_self_hash say for
+which steps the handle's self_hash_passes counter has to grow and for which it must not.
 
 build_plan() gives the steps; Expect(files) turns a step into its expected value -- plain lists and tuples of ints, in the
 same form tests/test_gpu_call_sequence.py brings the library's answers into -- from the suite's own checkers, computed
@@ -17,6 +19,7 @@ import os
 
 import numpy as np
 
+from tests import best_check as BC
 from tests import coverage_check as G
 from tests import fill_check as FC
 from tests import findere_check as F
@@ -26,17 +29,21 @@ from tests import positions_check as P
 from tests import prevalence_check as V
 from tests import set_quorum_check as Q
 from tests import sets_check as S
+from tests import similarity_check as SC
 from tests import weighted_check as W
 from tests import window_check as B
 
 FAMILIES = ("search_small", "search_large", "counts", "view", "positions", "prevalence", "weighted", "coverage", "sets",
-            "quorum", "set_prevalence", "groups", "doc_bits", "own_batch", "window", "window_positions", "adjusted")
+            "quorum", "set_prevalence", "groups", "doc_bits", "own_batch", "window", "window_positions", "adjusted", "best",
+            "similarity")
+NO_QUERIES = ("doc_bits", "similarity")                        # families whose call takes no query: they cannot fail
 SET_FAMILIES = ("sets", "quorum", "set_prevalence")
 KINDS = ("invalid_base", "too_short", "overflow")              # the failure steps
 CAN_FAIL = {
-    "invalid_base": tuple(f for f in FAMILIES if f != "doc_bits"),
-    "too_short": tuple(f for f in FAMILIES if f != "doc_bits"),
-    "overflow": ("search_small", "search_large", "view", "groups", "sets", "coverage", "weighted", "window"),
+    "invalid_base": tuple(f for f in FAMILIES if f not in NO_QUERIES),
+    "too_short": tuple(f for f in FAMILIES if f not in NO_QUERIES),
+    # (best.cpp caps its selection pool by hit_cap and selects again into a grown pool, as groups.cpp does)
+    "overflow": ("search_small", "search_large", "view", "groups", "sets", "coverage", "weighted", "window", "best"),
 }
 K_MAX = 31                                                     # the largest term size of the handles the plan is walked on
 ZS = (0, 3)
@@ -44,6 +51,7 @@ POLICIES = ("error", "miss", "skip")
 PASS_SMALL = 30000                                             # with the MANY batch: at least 3 device passes (see many_batch)
 PASS_BYTES = (0, PASS_SMALL)
 GRAPHS = (-1, 0)                                               # automatic | off
+SELF_HASH = (0, 2)                                             # scan_self_hash: never | wherever the shape allows
 SEARCHES = ((0.0, 0), (0.5, 0), (0.0, 3), (0.5, 3))
 QUORUMS = (0.5, 0.95, 1.0)
 WINDOWS = (7, 64, 300, 4095)                                   # one per plane count of the window scan (6, 8, 10, 12)
@@ -53,8 +61,19 @@ NQS_SMALL = (1, 2, 16)
 LABEL_STATES = ("initial", "relabel1", "relabel2", "cleared", "again")
 HIT_CAP_SMALL = 8
 OVERFLOW_T = 0.3
+SIMILARITY_REFS = (1, 8, 9, 17)                                # one reference, a full panel of 8, a panel and one, two and one
+# the self-hashing scan (kernels.hpp: scan_self_hash_fits): its LDS array holds 2048 + 64 row indices, (sub-indexes a tile
+# lies in) x (8-term blocks of the pass's longest query + 1) x 8 are needed
+SELF_HASH_ENTRIES = 2048 + 64
+# the families whose passes go through run_impl (no K1 of their own); own_batch: when it runs `counts`
+RUN_IMPL_FAMILIES = ("search_small", "search_large", "counts", "view", "groups", "best", "adjusted", "own_batch")
+SEARCH_FAMILIES = ("search_small", "search_large", "view", "adjusted")      # ... with the caller's threshold and limit
+OWN_K1_FAMILIES = ("positions", "prevalence", "weighted", "coverage", "window", "window_positions", "sets", "quorum",
+                   "set_prevalence")
+LONG_MAX = 700                                                 # positions of the longest query there is
+LONG_FITS = 520                                                # ... of the longest that still fits compact16's LDS array
 
-Step = collections.namedtuple("Step", "index family prev kind after z policy labels pass_bytes graph queries params")
+Step = collections.namedtuple("Step", "index family prev kind after z policy labels pass_bytes graph self_hash queries params")
 # kind: "regular" or one of KINDS; after: the kind of the failure step directly before this one, or None;
 # labels: the label state in force; params: a dict of what the family's call takes besides the queries
 
@@ -83,12 +102,19 @@ def euler_circuit(n, rng):
 
 
 def _setting_rows():
-    """14 rows (z, policy, pass_bytes, graph): the rows 0..5 hold every (z, policy) at pass_bytes 0, 6..11 at the small one;
-    graph is off in four rows that cover both z and both pass_bytes"""
+    """14 rows (z, policy, pass_bytes, graph, scan_self_hash): the rows 0..5 hold every (z, policy) at pass_bytes 0, 6..11
+    at the small one; graph is off in four rows that cover both z and both pass_bytes.  The self-hashing scan is on in
+    the rows 0, 2 and 4 -- z = 0 and pass_bytes = 0 under each policy: the rows of the `must` steps (MUST_ROWS) --, in 1 (z =
+    3: it has to stay on the table), in 6 and 10 (cut calls at z = 0) and in 9; row 12 is row 0's shape with the switch at 0"""
     rows = []
     for r in range(14):
-        rows.append((ZS[r % 2], POLICIES[(r // 2) % 3], PASS_BYTES[1 if 6 <= r < 12 else 0], GRAPHS[1 if r in (3, 8, 12, 13) else 0]))
+        rows.append((ZS[r % 2], POLICIES[(r // 2) % 3], PASS_BYTES[1 if 6 <= r < 12 else 0], GRAPHS[1 if r in (3, 8, 12, 13) else 0],
+                     SELF_HASH[1 if r in (0, 1, 2, 4, 6, 9, 10) else 0]))
     return rows
+
+
+MUST_ROWS = {"error": 0, "miss": 2, "skip": 4}                 # z = 0, pass_bytes = 0, the switch at 2
+TABLE_ROW = 12                                                 # z = 0, pass_bytes = 0, `error`, the switch at 0
 
 
 # the window of a window step follows its setting row: every W meets both z, both pass_bytes and all three policies in the
@@ -140,9 +166,9 @@ def _cut(src, rng, ln):
     return src[o:o + ln]
 
 
-def make_batch(rng, nq, z, has_long, with_n, many=False):
+def make_batch(rng, nq, z, has_long, with_n, many=False, long_max=LONG_MAX):
     """nq queries cut from the source: reads of K_MAX + z .. 150 characters (8-bit scores; the first is the shortest
-    allowed), with has_long one query of 300 .. 700 positions (16-bit scores) in the last place; with_n: an N in the middle
+    allowed), with has_long one query of 300 .. long_max positions (16-bit scores) in the last place; with_n: an N in the middle
     of query 1 (query 0 of a batch of one) and at the end of the last read.  many: the batch of the small pass_bytes: 24
     queries, reads of 120 .. 150 characters and two long queries -- more than 4500 characters, at 16 bytes of K1's table per
     character (four sub-indexes, one hash function, the narrow table: the least of the handles) more than 2 * PASS_SMALL"""
@@ -152,12 +178,17 @@ def make_batch(rng, nq, z, has_long, with_n, many=False):
     for i in range(nq):
         if many:
             ln = int(rng.integers(120, 151))
+            if with_n and i == 1:
+                # the read with the N in its middle is the longest there is: the N takes k + z positions out of it, and on
+                # either side of them enough stay for a window of 64 to reach half its width (a window hit for every query
+                # of the batch: hit_positions then looks all of them up, and the pass count of the step is known)
+                ln = 150
         else:
             ln = k + z if i == 0 else int(rng.integers(k + z, 151))
         qs.append(_cut(src, rng, ln))
     longs = ([nq - 1, nq // 2] if many else [nq - 1]) if has_long else []
     for i in longs:
-        qs[i] = _cut(src, rng, int(rng.integers(500 if many else 300, 601 if many else 701)) + k - 1 + z)
+        qs[i] = _cut(src, rng, int(rng.integers(500 if many else 300, 601 if many else long_max + 1)) + k - 1 + z)
     if with_n:
         i = 1 if nq > 1 else 0
         qs[i] = I.with_n(qs[i], [len(qs[i]) // 2])
@@ -256,21 +287,31 @@ def _query_count(fam, kind, j, many):
         return 1
     if kind == "overflow":
         return 16
+    if kind == "invalid_base" and fam in ("groups", "best"):
+        return 24                                                       # the bad query, the last, lies above index 16
     if fam == "search_small":
         return 16 if many else NQS_SMALL[j % 3]
     return 24 if many else NQS[(j + FAMILIES.index(fam)) % len(NQS)]
 
 
-def _step_queries(rng, fam, kind, j, z, policy, many, params):
-    """the queries of one step; a failure step of the kinds invalid_base and too_short gets its bad query (params["bad"])"""
+def _step_queries(rng, fam, kind, j, z, policy, many, params, row=None):
+    """the queries of one step; a failure step of the kinds invalid_base and too_short gets its bad query (params["bad"]).
+    Under the rows of the `must` steps the lengths are set, not drawn: `error` holds a 16-bit query that still fits the
+    self-hashing scan's LDS array on compact16, `miss` holds 8-bit queries only, `skip` holds an N and no query beyond
+    the array"""
     nq = _query_count(fam, kind, j, many)
     has_long = bool(many or rng.integers(2))
     with_n = policy != "error" and bool(rng.integers(3))
+    long_max = LONG_MAX
+    if row in MUST_ROWS.values():
+        long_max = LONG_FITS
+        has_long = {MUST_ROWS["error"]: True, MUST_ROWS["miss"]: False}.get(row, has_long)
+        with_n = with_n or (row == MUST_ROWS["skip"] and policy == "skip")      # (a failing step under `error` keeps its one N)
     if fam == "adjusted" and policy == "skip":
         with_n = True                                                   # P is the count of the valid positions, not T - z
     if kind == "overflow":
         has_long, with_n = False, False
-    queries = list(make_batch(rng, nq, z, has_long, with_n, many=many and nq == 24))
+    queries = list(make_batch(rng, nq, z, has_long, with_n, many=many and nq == 24, long_max=long_max))
     if kind == "invalid_base":
         bad = nq - 1 if nq > 1 else 0                                   # query i > 0 holds the N (counts has one query)
         queries[bad] = I.with_n(queries[bad], [len(queries[bad]) // 3])
@@ -286,6 +327,12 @@ def _family_params(fam, kind, i, j, nq, row, params):
     """what the family's call takes besides the queries (own_batch: see _own_batch_step); row: the step's setting row"""
     overflow = kind == "overflow"
     t, lim = (OVERFLOW_T, 0) if overflow else SEARCHES[(j + i) % 4]
+    if not overflow and fam in SEARCH_FAMILIES and row in (MUST_ROWS["error"], MUST_ROWS["miss"]):
+        t, lim = SEARCHES[(j + i) % 2]                                  # no limit: a top-k pass keeps K1's table
+        if fam == "view" and j >= len(_WINDOW_OF_ROW):
+            # ... but for the view call's second visit of its first row (build_plan: row 0, `error`, graph on): the top-k
+            # search at z = 0 and pass_bytes 0 with the switch at 2, which has to stay on the table
+            t, lim = SEARCHES[2 + (j + i) % 2]
     if fam in ("search_small", "search_large", "view", "weighted", "coverage", "adjusted"):
         params.update(t=t, lim=lim)
     elif fam == "window":
@@ -298,7 +345,17 @@ def _family_params(fam, kind, i, j, nq, row, params):
     elif fam == "quorum":
         params.update(quorum=QUORUMS[j % 3], t=(0.0, 0.3)[(j // 3) % 2], lim=(0, 2)[(j // 6) % 2])
     elif fam == "groups":
-        params.update(offsets=_group_offsets(nq, ("ones", "twos", "all")[j % 3]), t=t, rt=0.8, lim=lim)
+        # (the read threshold is the threshold of the pass: under `skip` a positive one takes K1's valid positions)
+        params.update(offsets=_group_offsets(nq, ("ones", "twos", "all")[j % 3]), t=t, rt=0.0 if row == MUST_ROWS["skip"] else 0.8, lim=lim)
+    elif fam == "best":
+        params.update(offsets=_group_offsets(nq, ("ones", "twos", "all")[j % 3]), t=t, lim=lim)
+    elif fam == "similarity":
+        # 1, 8, 9, 17 references: the first document of the first sub-index and the last of the last, partly filled one
+        # (one reference: one of the two in turn), the others drawn from the sub-index of `side` -- panels of 7, 8 and 16
+        # of one sub-index beside one of the other; of 8, 9 and 17 where the file has one sub-index; n = 9 repeats one
+        n = SIMILARITY_REFS[j % 4]
+        params.update(n=n, side=("first", "last")[(j // 4) % 2], picks=tuple(int(x) for x in np.random.default_rng(1000 * i + j).integers(0, 1 << 30, n)),
+                      repeat=n == 9)
 
 
 def _own_batch_step(own, kind, j, queries, z, policy, params):
@@ -319,6 +376,21 @@ def _own_batch_step(own, kind, j, queries, z, policy, params):
     return ("reread_" + own[1]["what"],) + own[1:], own[2]
 
 
+def _graph_form_steps(seq):
+    """{position: scan_self_hash} of the search_small steps that hold ONE batch at z = 0, `error`, pass_bytes 0 and graph on
+    with the switch at one value right after the other: a graph captured in one form must not be replayed in the other.
+    The circuit has search_small directly behind search_small once (every ordered pair occurs once): there the switch goes
+    0 -> 2.  The other order, 2 -> 0, is the pair around the too_short failure behind search_small: that call is refused on
+    the host, nothing is launched between the two."""
+    small = [i for i, (fam, kind, _a) in enumerate(seq) if fam == "search_small" and kind == "regular"]
+    loop = next(i for i in small if i + 1 in small)
+    fail = next(i for i, (_f, kind, _a) in enumerate(seq) if kind == "too_short" and seq[i + 1][0] == "search_small")
+    forms = {loop: 0, loop + 1: 2}
+    for pos, form in ((fail - 1, 2), (fail + 1, 0)):
+        assert forms.setdefault(pos, form) == form                      # (where the two meet they agree)
+    return forms
+
+
 def build_plan(seed=None):
     """-> list of Step.  Deterministic: the same seed gives the same plan."""
     seed = fuzz_seed() if seed is None else seed
@@ -329,40 +401,119 @@ def build_plan(seed=None):
     # the settings: per family a seeded permutation of the 14 rows, taken by the family's regular occurrences in turn
     rows = _setting_rows()
     perm = {f: [int(j) for j in rng.permutation(len(rows))] for f in FAMILIES}
+    perm["view"].remove(MUST_ROWS["error"])                             # the view call starts both its turns through the rows with
+    perm["view"].insert(0, MUST_ROWS["error"])                          # row 0: a `must` step first, a top-k search the second time
+    # own_batch runs `counts` every fourth step: those runs take the rows of the `must` steps and the table's first
+    count_rows = [int(r) for r in rng.permutation(list(MUST_ROWS.values()) + [TABLE_ROW])]
+    count_rows += [r for r in perm["own_batch"] if r not in count_rows]
+    forms = _graph_form_steps(seq)
+    form_batch = make_batch(rng, 2, 0, False, False)
     count = collections.Counter()
     steps, own, prev = [], None, None
     for i, (fam, kind, after) in enumerate(seq):
         j = count[fam]
         row = perm[fam][j % len(rows)]
-        z, policy, pass_bytes, graph = rows[row]
-        if kind == "regular":
+        if i in forms:
+            j = count[fam, "forms"]
+            count[fam, "forms"] += 1
+        elif fam == "own_batch" and kind == "regular" and own is not None and own[0] == "reread_topk":
+            j = count[fam, "counts"]                                    # (_own_batch_step: this one runs `counts`)
+            row = count_rows[j % len(rows)]
+            count[fam, "counts"] += 1
+        elif kind == "regular":
             count[fam] += 1
-        else:
+        z, policy, pass_bytes, graph, self_hash = rows[row]
+        if kind != "regular":
             pass_bytes = 0
             if kind == "invalid_base":
                 policy = "error"
+                if fam in ("search_large", "groups", "best"):          # the scan's own report of a bad query above index 16
+                    row = MUST_ROWS["error"]
+                    z, self_hash = rows[row][0], rows[row][4]
         params = {}
-        queries = _step_queries(rng, fam, kind, j, z, policy, pass_bytes != 0, params)
-        _family_params(fam, kind, i, j, len(queries), row, params)
+        if i in forms:
+            row = MUST_ROWS["error"]
+            (z, policy, pass_bytes, graph, _), self_hash = rows[row], forms[i]
+            queries = form_batch
+            params.update(t=0.5, lim=0)                                 # one shape class but for the form of the scan
+        else:
+            queries = _step_queries(rng, fam, kind, j, z, policy, pass_bytes != 0, params, row)
+            _family_params(fam, kind, i, j, len(queries), row, params)
         if fam == "own_batch":
             own, queries = _own_batch_step(own, kind, j, queries, z, policy, params)
-        steps.append(Step(i, fam, prev, kind, after, z, policy, states[i], pass_bytes, graph, queries, params))
+        steps.append(Step(i, fam, prev, kind, after, z, policy, states[i], pass_bytes, graph, self_hash, queries, params))
         prev = fam
     return steps
+
+
+# ---- the self-hashing scan ------------------------------------------------------------------------------------------------
+
+def _tile_sub_indexes(handle):
+    """the sub-indexes a tile of the scan lies in (kernels.hpp: scan_tile_pages).  compact16: four sub-indexes of one
+    16-byte chunk each, the tile is the index's four chunks wide (geometry.cpp: an index narrower than the tile)"""
+    assert handle == "compact16"
+    npages, cpp, tile_w = 4, 1, 4
+    return 1 if cpp % tile_w == 0 else min(npages, 1 + (tile_w - 1 + cpp - 1) // cpp)
+
+
+def self_hash_fits(handle, queries):
+    """does the LDS array of the self-hashing scan hold the row indices of a pass over `queries` (tests/test_gpu_self_hash.py:
+    _expect_self_hash)?  Multi-query work-groups are off on an index of fewer than 8 chunks."""
+    blocks = max((len(q) - K_MAX + 1 + 7) // 8 for q in queries)
+    return _tile_sub_indexes(handle) * (blocks + 1) * 8 <= SELF_HASH_ENTRIES
+
+
+def self_hash_handle(handle):
+    """can a pass on the handle take the self-hashing form at all (kernels.hpp: scan_has_self_hash)?  two_files holds a file
+    of 20-mers under three hash functions, two_files_idx64 has 64-bit row indices"""
+    return handle == "compact16"
+
+
+def _pass_threshold(st):
+    """the threshold the family hands to the pass (under `skip` a positive one takes K1's valid positions) and whether the
+    pass selects its top k (geometry.cpp: pass_self_hash)"""
+    fam, p = st.family, st.params
+    if fam in SEARCH_FAMILIES:
+        return p["t"], p["lim"] > 0
+    if fam == "groups":
+        return p["rt"], False
+    if fam == "own_batch":
+        return 0.0, p["what"] != "counts"
+    return 0.0, False                                                   # counts, best: threshold 0, filtered after the pass
+
+
+def must_self_hash(st, handle, kind="regular"):
+    """has self_hash_passes to grow over the step?  (kind: the invalid_base steps are asked with their own)"""
+    if st.kind != kind or not self_hash_handle(handle) or st.self_hash != 2 or st.z != 0 or st.pass_bytes != 0:
+        return False
+    if st.family not in RUN_IMPL_FAMILIES or st.params.get("what") == "reread":
+        return False
+    t, topk = _pass_threshold(st)
+    if topk or (st.policy == "skip" and t > 0):
+        return False
+    return self_hash_fits(handle, st.queries)
+
+
+def never_self_hash(st, handle):
+    """must self_hash_passes stay as it is over the step?  (positions: over its hit_positions call -- the search in front of
+    it is a host-buffer search like any other)"""
+    return (not self_hash_handle(handle) or st.self_hash == 0 or st.z != 0 or st.family in OWN_K1_FAMILIES
+            or st.family in NO_QUERIES)
 
 
 # ---- the device passes ----------------------------------------------------------------------------------------------------
 
 PASS_READERS = {"positions": "positions_ms", "prevalence": "prevalence_ms", "weighted": "weighted_ms", "coverage": "coverage_ms",
                 "sets": "sets_ms", "quorum": "set_quorum_ms", "set_prevalence": "set_quorum_ms", "window": "window_ms",
-                "window_positions": "positions_ms"}
+                "window_positions": "positions_ms", "best": "best_ms"}
 
 
 def needs_three_passes(st, expect):
     """must the step's call take at least 3 device passes (read off the family's *_ms reader)?  The small pass_bytes with
     the 24-query batch (make_batch: more than 2 * PASS_SMALL bytes of K1's table); hit_positions only looks up the queries
     that have a hit (window_positions: a window hit), and a set search without a labelled file has no work item; a
-    window search at threshold 0 adds its pool's bytes to the estimate: more passes, never fewer"""
+    window search at threshold 0 adds its pool's bytes to the estimate: more passes, never fewer.  (best: `best_ms` reads
+    the passes of the LAST call from cobs_gpu_best_counts, nothing is reset by reading)"""
     if st.kind != "regular" or st.family not in PASS_READERS or not st.pass_bytes or len(st.queries) != 24:
         return False
     if st.family in ("positions", "window_positions"):
@@ -501,6 +652,10 @@ class Expect:
             return (lists, [[int(x) for x in row] for row in P])
         if fam == "doc_bits":
             return [[int(x) for x in FC.bits_of_mats(fb.mats)] for fb in files]
+        if fam == "best":
+            return BC.results(files, list(qs), list(p["offsets"]), z, pol, p["t"], p["lim"])
+        if fam == "similarity":
+            return [[[int(x) for x in row] for row in SC.shared_of_index({"mats": fb.mats}, similarity_refs(st, fb))] for fb in files]
         assert fam == "own_batch"
         rz, rpol = (p["run_z"], p["run_policy"]) if p["what"] == "reread" else (z, pol)
         what = p["of"] if p["what"] == "reread" else p["what"]
@@ -522,8 +677,25 @@ class Expect:
         return any_in(v)
 
 
+def similarity_refs(st, fb):
+    """the references of a similarity step in one file (findere_check.FileBits): real documents"""
+    p = st.params
+    per = fb.mats[0].shape[1] * 8
+    first = range(0, min(per, fb.num_docs))
+    last = range((len(fb.mats) - 1) * per, fb.num_docs)
+    if p["n"] == 1:
+        return [first[0] if p["side"] == "first" else last[-1]]
+    pool = first if p["side"] == "first" else last
+    refs = [first[0]] + [pool[x % len(pool)] for x in p["picks"][2:]]
+    refs.insert(len(refs) // 2, last[-1])
+    if p["repeat"]:
+        refs[-1] = refs[1]
+    return refs
+
+
 def describe(st):
     """one line for an assertion message: the pair and the settings in force"""
-    return ("step %d: %s -> %s [%s%s] z=%d policy=%s labels=%s pass_bytes=%d graph=%d nq=%d lens=%s params=%s" % (
+    return ("step %d: %s -> %s [%s%s] z=%d policy=%s labels=%s pass_bytes=%d graph=%d self_hash=%d nq=%d lens=%s params=%s" % (
         st.index, st.prev, st.family, st.kind, (", after a failed " + st.after) if st.after else "", st.z, st.policy, st.labels,
-        st.pass_bytes, st.graph, len(st.queries), [len(q) for q in st.queries][:6], {k: v for k, v in st.params.items() if k != "offsets"}))
+        st.pass_bytes, st.graph, st.self_hash, len(st.queries), [len(q) for q in st.queries][:6],
+        {k: v for k, v in st.params.items() if k not in ("offsets", "picks")}))

@@ -29,14 +29,14 @@ def handles(tmp_path_factory):
 
 
 def test_every_ordered_pair_of_families(plan):
-    assert len(CS.FAMILIES) == 17 and len(set(CS.FAMILIES)) == 17
+    assert len(CS.FAMILIES) == 19 and len(set(CS.FAMILIES)) == 19 and {"best", "similarity"} < set(CS.FAMILIES)
     pairs = {(a.family, b.family) for a, b in zip(plan, plan[1:])}
     assert pairs == set(itertools.product(CS.FAMILIES, CS.FAMILIES))
     # ... and between two REGULAR steps too (the failure steps were put behind an occurrence of their follower's family)
     regular = {(a.family, b.family) for a, b in zip(plan, plan[1:]) if a.kind == "regular" and b.kind == "regular"}
     assert regular == set(itertools.product(CS.FAMILIES, CS.FAMILIES))
     assert all(st.index == i and st.prev == (plan[i - 1].family if i else None) for i, st in enumerate(plan))
-    assert len(plan) == 17 * 17 + 1 + 2 * 3 * 17
+    assert len(plan) == 19 * 19 + 1 + 2 * 3 * 19
 
 
 def test_every_family_meets_every_setting(plan):
@@ -47,6 +47,7 @@ def test_every_family_meets_every_setting(plan):
         assert {st.policy for st in mine} == set(CS.POLICIES), fam
         assert {st.pass_bytes for st in mine} == set(CS.PASS_BYTES), fam
         assert {st.graph for st in mine} == set(CS.GRAPHS), fam
+        assert {st.self_hash for st in mine} == set(CS.SELF_HASH), fam
     for fam in CS.SET_FAMILIES:
         assert {st.labels for st in regular if st.family == fam} == set(CS.LABEL_STATES), fam
     # every window (one per plane count of the scan) meets both z, both pass_bytes and all three policies
@@ -67,7 +68,8 @@ def test_every_family_meets_every_setting(plan):
     large = [st for st in plan if st.family == "search_large"]
     assert {len(st.queries) for st in large} == {24} and {st.kind for st in large} == {"regular"} | set(CS.KINDS)
     assert all(len(st.queries) == 16 for st in plan if st.kind == "overflow" and st.family != "search_large")
-    feature = [st for st in regular if st.family not in ("search_small", "search_large", "counts", "doc_bits", "own_batch", "adjusted")]
+    feature = [st for st in regular if st.family not in ("search_small", "search_large", "counts", "doc_bits", "own_batch", "adjusted",
+                                                         "similarity")]
     assert {len(st.queries) for st in feature} == set(CS.NQS)
     widths = [max(len(q) for q in st.queries) - CS.K_MAX + 1 - st.z > 255 for st in regular]
     assert sum(a != b for a, b in zip(widths, widths[1:])) > 40
@@ -86,6 +88,7 @@ def test_every_failure_kind_is_followed_by_every_family(plan):
         assert followers == set(CS.FAMILIES), kind
         failing = {st.family for st in plan if st.kind == kind}
         assert failing == set(CS.CAN_FAIL[kind]), kind                 # one failing call of every family that can fail this way
+        assert not set(CS.NO_QUERIES) & set(CS.CAN_FAIL[kind]) and "best" in CS.CAN_FAIL[kind]
     for a, b in zip(plan, plan[1:]):
         if a.kind != "regular":
             assert b.kind == "regular" and b.family != a.family and b.after == a.kind, CS.describe(b)
@@ -137,12 +140,24 @@ def test_the_expectations_are_not_vacuous(plan, handles, name):
     nonempty = {fam: 0 for fam in CS.FAMILIES}
     some_not_all = any_ne_all = partial_cover = n_matters = overflows = 0
     win_partial = win_some_not_all = win_n_matters = w_differs = adjusted_between = adjusted_skip_n = words_anchored = 0
+    best_not_first = best_ties = shared_pairs = 0
     whole_steps = set()
     for st in plan:
         if st.kind in ("invalid_base", "too_short"):
             continue
         v = ex.value(st)
         nonempty[st.family] += ex.nonempty(st)
+        if st.family == "best":
+            best_not_first += any(h[2] != offs for offs, hits in zip(st.params["offsets"], v) for h in hits)
+            best_ties += any(h[5] > 1 for hits in v for h in hits)
+        if st.family == "similarity":
+            for fb, rows in zip(files, v):
+                refs = CS.similarity_refs(st, fb)
+                bits = ex.value(st._replace(family="doc_bits"))[files.index(fb)]
+                per = fb.mats[0].shape[1] * 8
+                assert len(rows) == len(refs) == st.params["n"] and all(0 <= r < fb.num_docs for r in refs), CS.describe(st)
+                assert all(row[r % per] == bits[r] and len(row) == per for r, row in zip(refs, rows))      # shared(a, a) = bits(a)
+                shared_pairs += any(0 < x < bits[r] for r, row in zip(refs, rows) for x in row)
         if st.kind == "overflow":
             total = sum(len(x) for x in (v[0] if st.family in ("weighted", "groups") else v))
             assert total > CS.HIT_CAP_SMALL, CS.describe(st)            # the pool of HIT_CAP_SMALL records does overflow
@@ -197,8 +212,9 @@ def test_the_expectations_are_not_vacuous(plan, handles, name):
     assert all(nonempty.values()), nonempty
     assert win_partial > 0 and win_some_not_all > 0 and win_n_matters > 0 and (w_differs > 0 or len(files) == 1)
     assert adjusted_between > 0 and adjusted_skip_n > 0 and words_anchored > 500
+    assert best_not_first > 0 and best_ties > 0 and shared_pairs > 0
     assert whole_steps == {(fam, pol, z) for fam in ("positions", "window_positions") for pol in CS.POLICIES for z in CS.ZS}
-    assert some_not_all > 0 and any_ne_all > 0 and partial_cover > 0 and n_matters > 0 and overflows == len(CS.FAMILIES) == 17
+    assert some_not_all > 0 and any_ne_all > 0 and partial_cover > 0 and n_matters > 0 and overflows == len(CS.FAMILIES) == 19
     # a step without labels expects what the library documents: every query's list is empty (and the call succeeds)
     for st in plan:
         if st.family in CS.SET_FAMILIES and st.labels == "cleared" and st.kind == "regular":
@@ -227,6 +243,109 @@ def test_anchor_on_the_oracle(plan, handles, oracle):
         assert done >= 3
         st = next(st for st in plan if st.family == "counts" and st.kind == "regular" and st.z == 0 and b"N" not in st.queries[0])
         assert ex.value(st) == np.concatenate([ix.counts(st.queries[0]) for ix in ixs]).tolist()
+
+
+def test_anchor_best_and_similarity_on_their_checkers(plan, handles):
+    """one best step and one similarity step against the checkers' own top-level calls (best_check.results over the call's
+    arguments; similarity_check.shared_of_file, which reads the index FILE)"""
+    from tests import best_check as BC
+    from tests import similarity_check as SC
+    for name, (paths, files, ex) in handles.items():
+        st = next(st for st in plan if st.family == "best" and st.kind == "regular" and st.policy != "error"
+                  and any(b"N" in q for q in st.queries) and len(st.params["offsets"]) > 2)
+        want = BC.results(files, list(st.queries), list(st.params["offsets"]), st.z, st.policy, st.params["t"], st.params["lim"])
+        assert ex.value(st) == want and any(want), CS.describe(st)
+        assert all(type(x) is int for hits in ex.value(st) for h in hits for x in h)
+        st = next(st for st in plan if st.family == "similarity" and st.params["n"] == 17)
+        for path, fb, rows in zip(paths, files, ex.value(st)):
+            want = SC.shared_of_file(path, CS.similarity_refs(st, fb))
+            assert rows == [w.tolist() for w in want], CS.describe(st)
+
+
+def test_the_similarity_references(plan, handles):
+    mine = [st for st in plan if st.family == "similarity"]
+    assert {st.params["n"] for st in mine} == set(CS.SIMILARITY_REFS) and {st.kind for st in mine} == {"regular"}
+    in_one = set()                                                      # references of one sub-index in one call: the panels
+    repeats = 0
+    for name, (_paths, files, _ex) in handles.items():
+        for st in mine:
+            for fb in files:
+                refs = CS.similarity_refs(st, fb)
+                per = fb.mats[0].shape[1] * 8
+                subs = [r // per for r in refs]
+                in_one |= {subs.count(p) for p in set(subs)}
+                repeats += len(set(refs)) < len(refs)
+                if st.params["n"] > 1:                                  # the first sub-index and the last, partly filled one
+                    assert 0 in subs and len(fb.mats) - 1 in subs, CS.describe(st)
+                    assert fb.num_docs - 1 in refs and fb.num_docs % per != 0
+        ones = {CS.similarity_refs(st, files[-1])[0] // (files[-1].mats[0].shape[1] * 8) for st in mine if st.params["n"] == 1}
+        assert ones == {0, len(files[-1].mats) - 1}
+    assert {1, 7, 8, 9, 16, 17} <= in_one and repeats > 0               # the 8-reference panel's boundary and a second panel
+
+
+MUST_FAMILIES = ("search_small", "search_large", "counts", "view", "groups", "best", "adjusted", "own_batch")
+
+
+def test_the_self_hashing_steps(plan, handles):
+    """what the issue of the self-hashing walk asks of the plan, from the plan alone"""
+    h = "compact16"
+    assert set(CS.RUN_IMPL_FAMILIES) == set(MUST_FAMILIES)
+    must = [st for st in plan if CS.must_self_hash(st, h)]
+    never = [st for st in plan if CS.never_self_hash(st, h)]
+    assert not {st.index for st in must} & {st.index for st in never}
+    neither = [st for st in plan if st.kind == "regular" and not CS.must_self_hash(st, h) and not CS.never_self_hash(st, h)]
+    assert any(st.pass_bytes for st in neither) and len(must) >= 24
+    for other in ("two_files", "two_files_idx64"):
+        assert all(CS.never_self_hash(st, other) and not CS.must_self_hash(st, other) for st in plan)
+    for st in must:
+        assert st.kind == "regular" and st.self_hash == 2 and st.z == 0 and st.pass_bytes == 0 and st.family in MUST_FAMILIES
+        assert st.family not in CS.SEARCH_FAMILIES or st.params["lim"] == 0, CS.describe(st)      # (groups, best: cut on the host)
+        assert st.params.get("what", "counts") == "counts", CS.describe(st)
+        assert max(len(q) for q in st.queries) - CS.K_MAX + 1 <= 520 and CS.self_hash_fits(h, st.queries)
+        assert not (st.policy == "skip" and (st.params.get("rt", st.params.get("t", 0.0)) if st.family != "best" else 0.0) > 0)
+    for st in never:
+        assert (st.self_hash == 0 or st.z != 0 or st.family in CS.OWN_K1_FAMILIES + CS.NO_QUERIES), CS.describe(st)
+    # the LDS array's limit: 4 sub-indexes x (blocks + 1) x 8 <= 2112, 65 blocks, 520 terms
+    q = lambda terms: [b"A" * (terms + CS.K_MAX - 1)]
+    assert CS.self_hash_fits(h, q(520)) and not CS.self_hash_fits(h, q(521)) and CS.self_hash_fits(h, q(1))
+    assert CS.self_hash_handle(h) and not CS.self_hash_handle("two_files") and not CS.self_hash_handle("two_files_idx64")
+    for fam in MUST_FAMILIES:
+        mine = [st for st in must if st.family == fam]
+        assert {"error", "miss"} <= {st.policy for st in mine}, fam
+        # the same shape on the table path
+        assert any(st.family == fam and st.kind == "regular" and st.z == 0 and st.self_hash == 0 and st.pass_bytes == 0
+                   and st.params.get("what", "counts") == "counts" for st in plan), fam
+    for fam in ("counts", "groups", "best", "own_batch"):
+        assert any(st.family == fam and st.policy == "skip" and any(b"N" in q for q in st.queries) for st in must), fam
+    # a graph captured in one form and the other form right behind it, both ways round
+    small = {st.index: st for st in plan if st.family == "search_small" and st.kind == "regular"}
+    on_table = lambda st: st.self_hash == 0 and st.z == 0 and st.graph != 0 and st.pass_bytes == 0
+    hashing = lambda st: CS.must_self_hash(st, h) and st.graph != 0
+    same = lambda a, b: (a.queries, a.params, a.policy) == (b.queries, b.params, b.policy)
+    assert any(i + 1 in small and on_table(a) and hashing(small[i + 1]) and same(a, small[i + 1]) for i, a in small.items())
+    # (search_small is directly behind search_small once in the circuit: the other order is the pair around a call that
+    # the host refuses before anything is launched)
+    assert sum(i + 1 in small for i in small) == 1
+    assert any(i + 2 in small and hashing(a) and on_table(small[i + 2]) and same(a, small[i + 2]) and plan[i + 1].kind == "too_short"
+               for i, a in small.items())
+    # the scan's own report of an invalid base, from a query above index 16
+    for fam in ("search_large", "groups", "best"):
+        st = next(st for st in plan if st.family == fam and st.kind == "invalid_base")
+        assert CS.must_self_hash(st, h, "invalid_base") and st.params["bad"] > 16 and len(st.queries) == 24, CS.describe(st)
+        terms = [[len(q) - CS.K_MAX + 1 for q in st.queries] for st in must if st.family == fam]
+        assert any(256 <= max(t) <= 520 for t in terms) and any(max(t) <= 255 for t in terms), fam
+    # a step's expected value does not depend on the switch
+    # (Expect.value's memo key leaves the switch out; computed afresh for both values, not taken from the memo)
+    _paths, files, _ex = handles[h]
+    fresh = CS.Expect(files)
+    for st in [next(st for st in must if st.family == fam) for fam in MUST_FAMILIES]:
+        a, b = (fresh._value(s, s.family, s.queries, s.params, s.z, s.policy) for s in (st, st._replace(self_hash=0)))
+        assert a == b, CS.describe(st)
+    # a top-k host-buffer search at z = 0 and pass_bytes 0 with graph on and the switch at 2 stays in the plan (neither `must`
+    # nor `never`: it keeps K1's table), and so does a grouped search under `skip` at z = 0 with a positive read threshold
+    assert any(st.family in CS.SEARCH_FAMILIES and st.kind == "regular" and st.z == 0 and st.pass_bytes == 0 and st.graph != 0
+               and st.self_hash == 2 and st.policy in ("error", "miss") and st.params["lim"] > 0 for st in plan)
+    assert any(st.family == "groups" and st.kind == "regular" and st.z == 0 and st.policy == "skip" and st.params["rt"] > 0 for st in plan)
 
 
 def test_the_labels_of_every_state(handles):

@@ -1,11 +1,13 @@
 """GPU: every call family after every other on ONE handle (the plan of tests/call_sequence.py).  The host-buffer search, counts,
 the view call, hit positions, prevalence, the weighted, coverage, set, quorum and grouped searches, set prevalence,
-doc_bits, the window search (at one W per plane count of its scan), hit positions over window hits and the adjusted search
-(which under `skip` opens a short-lived Batch of its own) all work on the handle's scratch workspace; a long-lived Batch of
-the caller's lives beside it.  One Search and one Batch walk the whole plan -- every ordered pair of families, a failing
+doc_bits, the window search (at one W per plane count of its scan), hit positions over window hits, the adjusted search
+(which under `skip` opens a short-lived Batch of its own), the best-of-group search (two batches, a stream and a select of
+its own) and doc_shared_bits (a workspace of its own beside the fill cache of doc_bits) all work on the handle's scratch
+workspace or beside it; a long-lived Batch of the caller's lives beside it.  One Search and one Batch walk the whole plan -- every ordered pair of families, a failing
 call of every kind in front of every family, findere z, the invalid-bases policy, the labels, pass_bytes, graph, the query
-count and the score width changing between the steps -- and after EVERY step the answer is compared exactly with the
-checkers.  A failing step names the pair: the previous family, this family and the settings in force."""
+count, the score width and the form of the scan (tuning key scan_self_hash: K1's table or the self-hashing work-groups)
+changing between the steps -- and after EVERY step the answer is compared exactly with the checkers, and the handle's
+self_hash_passes counter with what call_sequence.must_self_hash / never_self_hash say about the step.  A failing step names the pair: the previous family, this family and the settings in force."""
 import gc
 import time
 
@@ -36,9 +38,11 @@ def _first_difference(got, want, path=""):
 
 
 class Walker:
-    def __init__(self, lib, search, batch, expect):
-        self.lib, self.s, self.b, self.ex = lib, search, batch, expect
+    def __init__(self, lib, search, batch, expect, handle):
+        self.lib, self.s, self.b, self.ex, self.handle = lib, search, batch, expect, handle
         self.z, self.policy, self.labels, self.pass_bytes, self.graph = 0, "error", None, 0, -1
+        self.self_hash = None                                           # (the shipped default, 1, is neither of the plan's)
+        self.not_mine = 0                                               # self-hashing passes of a step's call in front of the family's own
         self.floats = None                                              # (expected_fp, adjusted) of the last search_adjusted
 
     def settle(self, st):
@@ -55,7 +59,10 @@ class Walker:
             s.set_tuning("pass_bytes", st.pass_bytes)
         if st.graph != self.graph:
             s.set_tuning("graph", st.graph)
+        if st.self_hash != self.self_hash:
+            s.set_tuning("scan_self_hash", st.self_hash)
         self.z, self.policy, self.labels, self.pass_bytes, self.graph = st.z, st.policy, st.labels, st.pass_bytes, st.graph
+        self.self_hash = st.self_hash
         assert s.findere == st.z and s.invalid_bases == st.policy
 
     def call(self, st):
@@ -70,7 +77,9 @@ class Walker:
             offs, hits = s.search_view(qs, p["t"], p["lim"])
             return _lists(np.array(offs), np.array(hits))                # (views of the handle's arena: copied at once)
         if fam == "positions":
-            offs, hits = s.search_arrays(qs, 0.5, 0)
+            before = s.self_hash_passes
+            offs, hits = s.search_arrays(qs, 0.5, 0)                    # (a host-buffer search: it may well hash for itself)
+            self.not_mine = s.self_hash_passes - before
             bo, bits = s.hit_positions(qs, offs, hits)
             words = [bits[int(bo[h]):int(bo[h + 1])].tolist() for h in range(len(hits))]
             return (_lists(offs, hits), [words[int(offs[i]):int(offs[i + 1])] for i in range(len(qs))])
@@ -94,6 +103,10 @@ class Walker:
             return (_lists(offs, hits), pos.tolist())
         if fam == "doc_bits":
             return [s.doc_bits(f).tolist() for f in range(s.num_files)]
+        if fam == "best":
+            return _lists(*s.search_best_arrays(qs, list(p["offsets"]), p["t"], p["lim"]))
+        if fam == "similarity":
+            return [[row.tolist() for row in s.doc_shared_bits(CS.similarity_refs(st, fb), f)] for f, fb in enumerate(self.ex.files)]
         if fam == "window":
             return _lists(*s.search_window_arrays(qs, p["W"], p["t"], p["lim"]))
         if fam == "window_positions":
@@ -155,9 +168,23 @@ class Walker:
                     assert abs(a - b) <= 1e-12 * abs(b), "%s\n  result %d: %s %r, expected %r" % (CS.describe(st), r, name, a, b)
 
     def step(self, st):
-        from cobs_amd import _capi
+        """the step, and what it did to the handle's self_hash_passes counter"""
         s = self.s
         self.settle(st)
+        self.not_mine = 0
+        before = s.self_hash_passes
+        self.step_call(st)
+        grew = s.self_hash_passes - before - self.not_mine
+        if CS.must_self_hash(st, self.handle):
+            assert grew >= 1, "%s\n  no pass of the step took the self-hashing form" % CS.describe(st)
+        if CS.must_self_hash(st, self.handle, "invalid_base"):         # (the scan itself found the bad query)
+            assert grew >= 1, "%s\n  the failing pass did not take the self-hashing form" % CS.describe(st)
+        if CS.never_self_hash(st, self.handle):
+            assert grew == 0, "%s\n  %d passes of the step took the self-hashing form" % (CS.describe(st), grew)
+
+    def step_call(self, st):
+        from cobs_amd import _capi
+        s = self.s
         if st.kind in ("invalid_base", "too_short"):
             status = _capi.ERR_INVALID_BASE if st.kind == "invalid_base" else _capi.ERR_QUERY_TOO_SHORT
             try:
@@ -189,7 +216,10 @@ class Walker:
             # the same call three times: plain, captured, replayed (host_pass_begin: candidate, capture, replay)
             before = s.graph_replays
             for n, name in enumerate(("plain", "capture", "replay")):
+                hashed = s.self_hash_passes
                 self.check(st, self.call(st), " (call %d: %s)" % (n, name))
+                if CS.must_self_hash(st, self.handle):                  # the capture and the replay count like the plain pass
+                    assert s.self_hash_passes > hashed, "%s\n  call %d (%s) did not take the self-hashing form" % (CS.describe(st), n, name)
             grew = s.graph_replays - before
             if st.graph == 0:
                 assert grew == 0, "%s\n  graph is off and graph_replays grew by %d" % (CS.describe(st), grew)
@@ -230,7 +260,7 @@ def test_every_family_after_every_other_on_one_handle(gpu_lib, monkeypatch, tmp_
     def walk(steps):
         s = gpu_lib.Search(paths if len(paths) > 1 else paths[0])
         b = gpu_lib.Batch(s)
-        w = Walker(gpu_lib, s, b, ex)
+        w = Walker(gpu_lib, s, b, ex, handle)
         t0 = time.perf_counter()
         for st in steps:
             try:
@@ -238,7 +268,7 @@ def test_every_family_after_every_other_on_one_handle(gpu_lib, monkeypatch, tmp_
             except gpu_lib.CobsGpuError as e:
                 raise AssertionError("%s\n  raised %r" % (CS.describe(st), e))
         wall = time.perf_counter() - t0
-        stats = (s.graph_replays, s.host_passes)
+        stats = (s.graph_replays, s.host_passes, s.self_hash_passes)
         b.close()
         s.close()
         assert not s._h
@@ -249,8 +279,10 @@ def test_every_family_after_every_other_on_one_handle(gpu_lib, monkeypatch, tmp_
         torch.cuda.synchronize()
         return torch.cuda.mem_get_info()[0]
 
-    wall, (replays, passes) = walk(plan)
-    print("%s: %d steps walked in %.2f s, %d graph replays, %d host passes" % (handle, len(plan), wall, replays, passes))
+    wall, (replays, passes, hashed) = walk(plan)
+    print("%s: %d steps walked in %.2f s, %d graph replays, %d host passes, %d self_hash_passes" % (
+        handle, len(plan), wall, replays, passes, hashed))
+    assert (hashed > 0) == CS.self_hash_handle(handle)
     # no device memory is left: as the leak tests of the suite measure it, over repeated open / walk / close cycles (the
     # whole walk above was the first).  A cycle walks the shortest start of the plan that reaches every family and a failure step.  The bound is 64 KiB per
     # cycle: a handle keeps at least its index on the device, and the smallest index file here has 66 KiB of rows, so a
