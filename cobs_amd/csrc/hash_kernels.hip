@@ -47,12 +47,13 @@ __device__ __forceinline__ void add_valid_position(uint32_t* valid, uint32_t q, 
 }
 
 // invalid_bases = skip: the thresholds of one file from K1's valid positions, ceil(threshold * V) in double as the host's
-// threshold_for computes it -- and at least 1: a query without a valid position matches nothing, not everything.
+// threshold_for computes it -- and at least 1: a query without a valid position matches nothing, not everything.  A
+// threshold that is not > 0 (a NaN too) asks for every document, as threshold_of says on the host: 0.
 __global__ __launch_bounds__(256) void skip_thresholds_kernel(SkipThresholdArgs a) {
     const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= a.nq) return;
     const double v = ceil(a.threshold * (double)a.valid[q]);
-    a.thresholds[q] = !(v >= 1.0) ? 1u : v >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)v;
+    a.thresholds[q] = !(a.threshold > 0.0) ? 0u : !(v >= 1.0) ? 1u : v >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)v;
 }
 
 template <typename IdxT>

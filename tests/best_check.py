@@ -15,11 +15,11 @@ fraction equals the best one's (the best one included).  A document is reported 
 positions)) (in double; every real document when threshold <= 0); a group without members reports nothing.  A group's
 records: by fraction descending (exact), then score descending, then (file, doc); num_results cuts the list.
 """
-import math
 from fractions import Fraction
 
 import numpy as np
 
+from tests import findere_check as F
 from tests import groups_check as G
 
 NONE = 0xFFFFFFFF
@@ -98,7 +98,7 @@ def cells(files, queries, offsets, z=0, mode="error"):
 def threshold_of(threshold, positions):
     if not threshold > 0:
         return 0
-    return max(1, int(math.ceil(threshold * float(positions))))
+    return max(1, F.ceil_product(threshold, positions))
 
 
 def order_key(h):

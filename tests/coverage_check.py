@@ -11,10 +11,10 @@ For threshold > 0 a real document is a hit when coverage >= max(1, ceil(threshol
 every real document is returned.  The denominator is L under both invalid-bases policies, so `miss` and `skip` give the
 same result.  Per query the records are ordered by coverage descending, then (file, document) ascending, and cut to
 num_results when it is > 0 (the reference's index-order rule does not apply)."""
-import math
 
 import numpy as np
 
+from tests import findere_check as F
 from tests import prevalence_check as V
 
 
@@ -75,7 +75,7 @@ def thresholds(threshold, length):
     """the covered bases a document has to reach for a query of `length` characters (0: every real document)"""
     if not threshold > 0:
         return 0
-    return max(1, int(math.ceil(threshold * float(length))))
+    return max(1, F.ceil_product(threshold, length))
 
 
 def tables(files, q, z, mode="error"):

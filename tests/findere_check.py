@@ -68,9 +68,20 @@ def counts(files, q, z):
     return np.concatenate([f.scores(q, z) for f in files])
 
 
+BOUND_LIMIT = 2 ** 32 - 1
+
+
+def ceil_product(threshold, positions, limit=BOUND_LIMIT):
+    """ceil(threshold * positions) with the product in double, as an integer: 0 when the product is not > 0 (a NaN
+    threshold, inf * 0), `limit` from there on (an infinite or huge threshold: no score reaches it)"""
+    v = float(threshold) * float(positions)
+    if not v > 0:
+        return 0
+    return limit if v >= float(limit) else int(math.ceil(v))
+
+
 def threshold_for(threshold, positions):
-    v = math.ceil(threshold * float(positions))
-    return 0 if not v > 0 else int(v)
+    return ceil_product(threshold, positions)
 
 
 def results(files, q, z, threshold=0.0, num_results=0):

@@ -10,7 +10,6 @@ Group g is the queries [offsets[g], offsets[g + 1]).  Per (group, file, document
 A group's result: the real documents with sum >= max(1, ceil(threshold * P)) (every real document when threshold <= 0),
 by sum descending, then (file, document); num_results cuts the list.  No "single hash in total: index order" rule.
 """
-import math
 
 import numpy as np
 
@@ -63,7 +62,7 @@ def totals(files, queries, offsets, z=0, mode="error", read_threshold=0.0):
 def group_threshold(threshold, positions):
     if not threshold > 0:
         return 0
-    return max(1, int(math.ceil(threshold * float(positions))))
+    return max(1, F.ceil_product(threshold, positions, 2 ** 64 - 1))      # (64-bit sums: clamped at 2^64 - 1)
 
 
 def results(files, queries, offsets, z=0, mode="error", threshold=0.0, read_threshold=0.0, num_results=0):

@@ -11,6 +11,7 @@ import math
 
 import numpy as np
 
+from tests import findere_check as F
 from tests import invalid_check as I
 from tests import prevalence_check as V
 
@@ -63,6 +64,8 @@ def profile(fb, q, z, labels, mode="error"):
 
 def need(quorum, m):
     """max(1, ceil(quorum * members)): the double product, as the library's host code forms it"""
+    if not (quorum > 0 and quorum <= 1):
+        raise ValueError("quorum: a number in (0, 1] (the call refuses every other)")
     return max(1, int(math.ceil(float(quorum) * float(m))))
 
 
@@ -85,8 +88,10 @@ def denominator(fb, q, z, mode="error"):
 
 
 def threshold_for(t, P):
-    """max(1, ceil(t * P)) in double"""
-    return max(1, int(math.ceil(float(t) * float(P))))
+    """max(1, ceil(t * P)) in double for t > 0; 0 (every non-empty set) otherwise"""
+    if not t > 0:
+        return 0
+    return max(1, F.ceil_product(t, P))
 
 
 def results(files, labelings, q, z, quorum, threshold=0.0, num_results=0, mode="error"):

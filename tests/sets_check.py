@@ -6,10 +6,10 @@ of the real documents that carry its label -- padding slots and unlabelled docum
 its key reaches max(1, ceil(threshold * P)), P = n, or under `skip` the valid positions of invalid_check; threshold <= 0
 returns every non-empty set.  Records are ordered by key descending, the other count descending, (file, set) ascending.
 No engine code in it."""
-import math
 
 import numpy as np
 
+from tests import findere_check as F
 from tests import invalid_check as I
 from tests import prevalence_check as V
 
@@ -61,8 +61,10 @@ def denominator(fb, q, z, mode="error"):
 
 
 def threshold_for(t, P):
-    """max(1, ceil(t * P)) in double"""
-    return max(1, int(math.ceil(float(t) * float(P))))
+    """max(1, ceil(t * P)) in double for t > 0; 0 (every non-empty set) otherwise"""
+    if not t > 0:
+        return 0
+    return max(1, F.ceil_product(t, P))
 
 
 def results(files, labelings, q, z, threshold=0.0, rank_by="any", num_results=0, mode="error"):

@@ -12,10 +12,10 @@ threshold > 0 a real document is a hit when score >= max(1, ceil(threshold * W))
 for threshold <= 0 every real document is returned.  Per query the records are ordered by score descending, then (file,
 document) ascending, and cut to num_results when it is > 0 (the reference's index-order rule does not apply).  A
 position nobody holds weighs 0, so the policies `miss` and `skip` give the same result."""
-import math
 
 import numpy as np
 
+from tests import findere_check as F
 from tests import prevalence_check as V
 
 
@@ -52,7 +52,7 @@ def thresholds(threshold, total):
     """the score a document of a (query, file) with total weight `total` has to reach (0: every real document)"""
     if not threshold > 0:
         return 0
-    return max(1, int(math.ceil(threshold * float(total))))
+    return max(1, F.ceil_product(threshold, total))
 
 
 def total_weights(files, q, z, mode="error"):

@@ -9,10 +9,10 @@ For threshold > 0 a real document is a hit when best >= max(1, ceil(threshold * 
 real document is returned.  The denominator is w under both invalid-bases policies, so `miss` and `skip` give the same
 result.  Per query the records are ordered by best descending, then (file, document) ascending, and cut to num_results
 when it is > 0 (the reference's index-order rule does not apply)."""
-import math
 
 import numpy as np
 
+from tests import findere_check as F
 from tests import prevalence_check as V
 
 
@@ -68,7 +68,7 @@ def thresholds(threshold, w):
     """the set positions a window of w positions has to hold (0: every real document)"""
     if not threshold > 0:
         return 0
-    return max(1, int(math.ceil(threshold * float(w))))
+    return max(1, F.ceil_product(threshold, w))
 
 
 def tables(files, q, z, W, mode="error"):
