@@ -4,7 +4,8 @@
 // kept, over two alternating scratch batches on one stream --; behind every pass's scan group_best_kernel merges its
 // score rows into the per-(group, slot) state of the best member where they lie (best_kernels.hip), so the host stages
 // pass i + 1 while the device scans pass i.  After the last pass the select kernel appends the documents whose best
-// member reaches its threshold to a pool; the host orders each group's records.  No per-query result leaves the device.
+// member reaches its threshold to a pool (its retry: pooled_pass.hpp); the host orders each group's records
+// (pooled_call.hpp: hand_out_lists).  No per-query result leaves the device.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -14,6 +15,7 @@
 
 #include "best_kernels.hpp"
 #include "engine.hpp"
+#include "pooled_pass.hpp"
 
 namespace cobs_amd {
 
@@ -28,8 +30,7 @@ struct BestWork {
     DevBuf<uint8_t> d_args[2];
     DevBuf<uint32_t> state;                 // four arrays [n_groups][local_counts], for the lifetime of a call
     DevBuf<uint32_t> part;                  // four arrays [pieces][local_counts]: the partial states of a pass's split groups
-    DevBuf<BestRec> pool;
-    DevBuf<unsigned long long> fill;
+    HitPool<BestRec> hits{"best: the selection pool", launch_group_zero};
     DevBuf<GroupRange> ranges;
     double ms[3] = {0, 0, 0};               // best and merge kernels | select | host ordering of the last call
     uint64_t counts[4] = {0, 0, 0, 0};      // passes | spans that own their cells | partial states | folds of the last call
@@ -72,7 +73,6 @@ cobs_gpu_status init_work(cobs_gpu_index* ix) {
     for (auto& b : w->batch)
         if (!b)
             if (cobs_gpu_status st = cobs_gpu_batch_create(ix, 0, 0, &b); st != COBS_GPU_OK) return st;
-    HIP_TRY(w->fill.reserve(2));
     return COBS_GPU_OK;
 }
 
@@ -200,7 +200,6 @@ cobs_gpu_status pass_end(const Call& c, const Pass& ps) {
 // a before b in a group's list: the larger fraction (exact; positions = 0 is the fraction 0), then the larger score, then
 // (file, document)
 bool record_before(const BestRec& a, const BestRec& b) {
-    if (a.group != b.group) return a.group < b.group;
     const uint64_t x = (uint64_t)a.score * std::max(b.positions, 1u), y = (uint64_t)b.score * std::max(a.positions, 1u);
     if (x != y) return x > y;
     if (a.score != b.score) return a.score > b.score;
@@ -222,7 +221,6 @@ cobs_gpu_status search_best_impl(cobs_gpu_index* ix, const char* const* queries,
     if (ix->hbm_budget != 0 || any_streamed(ix)) return fail(COBS_GPU_ERR_UNSUPPORTED, "best: not on a handle with an HBM budget (its score rows come range by range)");
     if (ix->shard_count > 1) return fail(COBS_GPU_ERR_UNSUPPORTED, "best: not on one shard of several (a shard holds a part of every file's documents; ask every shard)");
     for (size_t g = 0; g <= n_groups; ++g) hit_offsets[g] = 0;
-    const size_t nf = ix->parts.size();
     const uint32_t z = ix->findere;
     // everything the host can refuse is refused before anything is launched
     cobs_gpu_status refused = check_query_lengths(ix, queries, lens, nq, z, [&](size_t q) -> cobs_gpu_status {
@@ -287,83 +285,42 @@ cobs_gpu_status search_best_impl(cobs_gpu_index* ix, const char* const* queries,
         if (cobs_gpu_status s = pass_end(call, inflight.front()); s != COBS_GPU_OK) { drain(); return s; }
     HIP_TRY(hipStreamSynchronize(st));
 
-    // ---- selection: real documents whose best member has score >= max(1, ceil(threshold * positions)) (threshold <= 0:
-    // every real document of a group with members)
-    std::vector<GroupRange> ranges;
-    uint64_t real_total = 0;
-    for (size_t f = 0; f < nf; ++f) {
-        const Part& p = ix->parts[f];
-        const uint64_t docs = p.meta.doc_names.size();
-        const uint64_t real = docs > p.slot_begin ? std::min<uint64_t>(docs - p.slot_begin, p.slot_count) : 0;
-        if (real) ranges.push_back(GroupRange{(uint32_t)p.local_offset, (uint32_t)(p.local_offset + real), (uint32_t)p.slot_begin, (uint32_t)f});
-        real_total += real;
-    }
+    // ---- selection: real documents whose best member's score reaches the bound the select kernel forms from `threshold`
+    // and the member's positions (min_key's rule, on the device; threshold <= 0: every real document of a group with
+    // members).  The state stays where it is while the pool takes its retry (pooled_pass.hpp)
+    const std::vector<GroupRange> ranges = real_ranges<GroupRange>(*ix);
     std::vector<BestRec> recs;
     if (!ranges.empty()) {
         HIP_TRY(w->ranges.reserve(ranges.size()));
         HIP_TRY(hipMemcpy(w->ranges.p, ranges.data(), ranges.size() * sizeof(GroupRange), hipMemcpyHostToDevice));
-        // the first guess of the pool (tuning key hit_cap: a small one, so that tests reach the overflow path); a pool that
-        // overflows is grown to the fill the kernel reports and the selection alone runs again -- the state stays
-        uint64_t pool_cap = threshold > 0.0 ? std::min<uint64_t>(real_total * n_groups, std::max<uint64_t>(1u << 20, n_groups * 1024ull))
-                                            : real_total * n_groups;
-        if (ix->tune.hit_cap) pool_cap = std::min<uint64_t>(pool_cap, ix->tune.hit_cap);
-        pool_cap = std::max<uint64_t>(pool_cap, 1);
-        unsigned long long fill = 0;
-        for (int attempt = 0; attempt < 2; ++attempt) {
-            if (w->pool.reserve((size_t)pool_cap) != hipSuccess) {
-                (void)hipGetLastError();
-                return fail(COBS_GPU_ERR_CAPACITY, "no room for " + std::to_string(pool_cap) + " best records; raise the threshold or use fewer groups per call");
-            }
-            HIP_TRY(launch_group_zero(reinterpret_cast<uint32_t*>(w->fill.p), 2, st));
-            BestSelArgs sa{};
-            sa.state = state;
-            sa.ranges = w->ranges.p;
-            sa.pool = w->pool.p;
-            sa.fill = w->fill.p;
-            sa.nslots = nslots;
-            sa.cap = pool_cap;
-            sa.threshold = threshold;
-            sa.n_groups = (uint32_t)n_groups;
-            sa.nranges = (uint32_t)ranges.size();
-            HIP_TRY(hipEventRecord(w->ev_sel[0], st));
-            HIP_TRY(launch_group_best_select(sa, st));
-            HIP_TRY(hipEventRecord(w->ev_sel[1], st));
-            HIP_TRY(hipMemcpyAsync(&fill, w->fill.p, sizeof fill, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            float ms = 0;
-            if (hipEventElapsedTime(&ms, w->ev_sel[0], w->ev_sel[1]) == hipSuccess) w->ms[1] += ms;
-            else (void)hipGetLastError();
-            if (fill <= pool_cap) break;
-            pool_cap = fill;
-        }
-        if (fill > pool_cap) return fail(COBS_GPU_ERR_HIP, "best: the selection pool overflowed twice");
-        recs.resize((size_t)fill);
-        if (fill) HIP_TRY(hipMemcpy(recs.data(), w->pool.p, (size_t)fill * sizeof(BestRec), hipMemcpyDeviceToHost));
+        uint64_t fill = 0;
+        cobs_gpu_status s = select_through(w->hits, first_pool_cap(ix->tune.hit_cap, threshold, real_documents(*ix), n_groups), st, w->ev_sel, &w->ms[1],
+            [](uint64_t cap) {
+                return fail(COBS_GPU_ERR_CAPACITY, "no room for " + std::to_string(cap) + " best records; raise the threshold or use fewer groups per call");
+            },
+            [&](uint64_t pool_cap) {
+                BestSelArgs sa{};
+                sa.state = state;
+                sa.ranges = w->ranges.p;
+                sa.pool = w->hits.pool.p;
+                sa.fill = w->hits.fill.p;
+                sa.nslots = nslots;
+                sa.cap = pool_cap;
+                sa.threshold = threshold;
+                sa.n_groups = (uint32_t)n_groups;
+                sa.nranges = (uint32_t)ranges.size();
+                return launch_group_best_select(sa, st);
+            }, &fill);
+        if (s != COBS_GPU_OK) return s;
+        if (cobs_gpu_status c = append_records(recs, w->hits.pool.p, fill); c != COBS_GPU_OK) return c;
     }
     // ---- ordering: per group by fraction descending, then score descending, then (file, document); num_results cuts
     const double t0 = now_s();
-    std::sort(recs.begin(), recs.end(), record_before);
-    std::vector<size_t> first(n_groups + 1, 0);
-    for (const BestRec& r : recs) first[r.group + 1]++;
-    for (size_t g = 0; g < n_groups; ++g) first[g + 1] += first[g];
-    size_t used = 0;
-    for (size_t g = 0; g < n_groups; ++g) {
-        const size_t have = first[g + 1] - first[g];
-        used += num_results ? std::min(have, num_results) : have;
-        hit_offsets[g + 1] = used;
-    }
-    if (used > cap) {
-        w->ms[2] = (now_s() - t0) * 1e3;
-        return fail(COBS_GPU_ERR_CAPACITY, "result buffer too small; hit_offsets[n_groups] holds the needed size");
-    }
-    for (size_t g = 0; g < n_groups; ++g) {
-        const BestRec* r = recs.data() + first[g];
-        cobs_gpu_best_hit* out = hits + hit_offsets[g];
-        for (size_t i = 0, n = hit_offsets[g + 1] - hit_offsets[g]; i < n; ++i)
-            out[i] = cobs_gpu_best_hit{r[i].file, r[i].doc, r[i].query, r[i].score, r[i].positions, r[i].ties};
-    }
+    const cobs_gpu_status handed = hand_out_lists(recs, n_groups, [](const BestRec& r) { return r.group; }, record_before,
+        num_results, hits, cap, hit_offsets, "n_groups",
+        [](const BestRec& r) { return cobs_gpu_best_hit{r.file, r.doc, r.query, r.score, r.positions, r.ties}; });
     w->ms[2] = (now_s() - t0) * 1e3;
-    return COBS_GPU_OK;
+    return handed;
 }
 
 }  // namespace

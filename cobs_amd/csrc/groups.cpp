@@ -3,18 +3,19 @@
 // K2 with the read threshold, over two alternating scratch batches on one stream --; behind every pass's scan the
 // accumulate kernel adds its score rows to the per-group sums and votes where they lie (group_kernels.hip), so the host
 // stages pass i + 1 while the device scans and accumulates pass i.  After the last pass the select kernel appends the
-// documents that reach their group's threshold to a pool; the host orders each group's records.  Not threaded through
+// documents that reach their group's threshold to a pool (its retry: pooled_pass.hpp); the host orders each group's
+// records (pooled_call.hpp: hand_out_lists).  Not threaded through
 // the pipelined collect paths of cobs_gpu_search_batch (host_api.cpp): no per-query result ever leaves the device.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
-#include <cmath>
 #include <cstring>
 #include <string>
 #include <vector>
 
 #include "engine.hpp"
 #include "group_kernels.hpp"
+#include "pooled_pass.hpp"
 
 namespace cobs_amd {
 
@@ -28,8 +29,7 @@ struct GroupsWork {
     PinnedBuf<uint8_t> h_args[2];           // files | spans of a pass, as the accumulate kernel reads them
     DevBuf<uint8_t> d_args[2];
     DevBuf<uint32_t> acc_sum, acc_votes;    // [n_groups][local_counts], for the lifetime of a call
-    DevBuf<GroupRec> pool;
-    DevBuf<unsigned long long> fill;
+    HitPool<GroupRec> hits{"groups: the selection pool", launch_group_zero};
     DevBuf<GroupRange> ranges;
     DevBuf<uint64_t> gthr;
     double ms[3] = {0, 0, 0};               // accumulate | select | host ordering of the last call
@@ -71,7 +71,6 @@ cobs_gpu_status init_work(cobs_gpu_index* ix) {
     for (auto& b : w->batch)
         if (!b)
             if (cobs_gpu_status st = cobs_gpu_batch_create(ix, 0, 0, &b); st != COBS_GPU_OK) return st;
-    HIP_TRY(w->fill.reserve(2));
     return COBS_GPU_OK;
 }
 
@@ -267,97 +266,51 @@ cobs_gpu_status search_groups_impl(cobs_gpu_index* ix, const char* const* querie
     HIP_TRY(hipStreamSynchronize(st));
     if (positions) std::memcpy(positions, pos.data(), pos.size() * sizeof(uint64_t));
 
-    // ---- selection: real documents whose sum reaches gthr = max(1, ceil(threshold * P)) (threshold <= 0: all of them)
-    std::vector<GroupRange> ranges;
-    uint64_t real_total = 0;
-    for (size_t f = 0; f < nf; ++f) {
-        const Part& p = ix->parts[f];
-        const uint64_t docs = p.meta.doc_names.size();
-        const uint64_t real = docs > p.slot_begin ? std::min<uint64_t>(docs - p.slot_begin, p.slot_count) : 0;
-        if (real) ranges.push_back(GroupRange{(uint32_t)p.local_offset, (uint32_t)(p.local_offset + real), (uint32_t)p.slot_begin, (uint32_t)f});
-        real_total += real;
-    }
+    // ---- selection: real documents whose sum reaches gthr = min_key(threshold, P) (pooled_call.hpp; 0: all of them).  The
+    // accumulators stay where they are while the pool takes its retry (pooled_pass.hpp)
+    const std::vector<GroupRange> ranges = real_ranges<GroupRange>(*ix);
     std::vector<uint64_t> gthr(nf * n_groups, 0);
-    if (threshold > 0.0)
-        for (size_t f = 0; f < nf; ++f)
-            for (size_t g = 0; g < n_groups; ++g) {
-                const double v = std::ceil(threshold * (double)pos[g * nf + f]);
-                gthr[f * n_groups + g] = !(v > 1.0) ? 1ull : v >= 18446744073709549568.0 ? ~0ull : (uint64_t)v;
-            }
+    for (size_t f = 0; f < nf; ++f)
+        for (size_t g = 0; g < n_groups; ++g) gthr[f * n_groups + g] = min_key<uint64_t>(threshold, pos[g * nf + f]);
     std::vector<GroupRec> recs;
     if (!ranges.empty()) {
         HIP_TRY(w->ranges.reserve(ranges.size()));
         HIP_TRY(w->gthr.reserve(gthr.size()));
         HIP_TRY(hipMemcpy(w->ranges.p, ranges.data(), ranges.size() * sizeof(GroupRange), hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(w->gthr.p, gthr.data(), gthr.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
-        // the first guess of the pool (tuning key hit_cap: a small one, so that tests reach the overflow path); a pool that
-        // overflows is grown to the fill the kernel reports and the selection alone runs again -- the accumulators stay
-        uint64_t pool_cap = threshold > 0.0 ? std::min<uint64_t>(real_total * n_groups, std::max<uint64_t>(1u << 20, n_groups * 1024ull))
-                                            : real_total * n_groups;
-        if (ix->tune.hit_cap) pool_cap = std::min<uint64_t>(pool_cap, ix->tune.hit_cap);
-        pool_cap = std::max<uint64_t>(pool_cap, 1);
-        unsigned long long fill = 0;
-        for (int attempt = 0; attempt < 2; ++attempt) {
-            if (w->pool.reserve((size_t)pool_cap) != hipSuccess) {
-                (void)hipGetLastError();
-                return fail(COBS_GPU_ERR_CAPACITY, "no room for " + std::to_string(pool_cap) + " group records; raise the threshold or use fewer groups per call");
-            }
-            HIP_TRY(launch_group_zero(reinterpret_cast<uint32_t*>(w->fill.p), 2, st));
-            GroupSelArgs sa{};
-            sa.acc_sum = w->acc_sum.p;
-            sa.acc_votes = w->acc_votes.p;
-            sa.ranges = w->ranges.p;
-            sa.gthr = w->gthr.p;
-            sa.pool = w->pool.p;
-            sa.fill = w->fill.p;
-            sa.nslots = nslots;
-            sa.cap = pool_cap;
-            sa.n_groups = (uint32_t)n_groups;
-            sa.nranges = (uint32_t)ranges.size();
-            HIP_TRY(hipEventRecord(w->ev_sel[0], st));
-            HIP_TRY(launch_group_select(sa, st));
-            HIP_TRY(hipEventRecord(w->ev_sel[1], st));
-            HIP_TRY(hipMemcpyAsync(&fill, w->fill.p, sizeof fill, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            float ms = 0;
-            if (hipEventElapsedTime(&ms, w->ev_sel[0], w->ev_sel[1]) == hipSuccess) w->ms[1] += ms;
-            else (void)hipGetLastError();
-            if (fill <= pool_cap) break;
-            pool_cap = fill;
-        }
-        if (fill > pool_cap) return fail(COBS_GPU_ERR_HIP, "groups: the selection pool overflowed twice");
-        recs.resize((size_t)fill);
-        if (fill) HIP_TRY(hipMemcpy(recs.data(), w->pool.p, (size_t)fill * sizeof(GroupRec), hipMemcpyDeviceToHost));
+        uint64_t fill = 0;
+        cobs_gpu_status s = select_through(w->hits, first_pool_cap(ix->tune.hit_cap, threshold, real_documents(*ix), n_groups), st, w->ev_sel, &w->ms[1],
+            [](uint64_t cap) {
+                return fail(COBS_GPU_ERR_CAPACITY, "no room for " + std::to_string(cap) + " group records; raise the threshold or use fewer groups per call");
+            },
+            [&](uint64_t pool_cap) {
+                GroupSelArgs sa{};
+                sa.acc_sum = w->acc_sum.p;
+                sa.acc_votes = w->acc_votes.p;
+                sa.ranges = w->ranges.p;
+                sa.gthr = w->gthr.p;
+                sa.pool = w->hits.pool.p;
+                sa.fill = w->hits.fill.p;
+                sa.nslots = nslots;
+                sa.cap = pool_cap;
+                sa.n_groups = (uint32_t)n_groups;
+                sa.nranges = (uint32_t)ranges.size();
+                return launch_group_select(sa, st);
+            }, &fill);
+        if (s != COBS_GPU_OK) return s;
+        if (cobs_gpu_status c = append_records(recs, w->hits.pool.p, fill); c != COBS_GPU_OK) return c;
     }
     // ---- ordering: per group by sum descending, then (file, document) ascending; num_results cuts the list
     const double t0 = now_s();
-    std::sort(recs.begin(), recs.end(), [](const GroupRec& a, const GroupRec& b) {
-        if (a.group != b.group) return a.group < b.group;
-        if (a.sum != b.sum) return a.sum > b.sum;
-        if (a.file != b.file) return a.file < b.file;
-        return a.doc < b.doc;
-    });
-    std::vector<size_t> first(n_groups + 1, 0);
-    for (const GroupRec& r : recs) first[r.group + 1]++;
-    for (size_t g = 0; g < n_groups; ++g) first[g + 1] += first[g];
-    size_t used = 0;
-    for (size_t g = 0; g < n_groups; ++g) {
-        const size_t have = first[g + 1] - first[g];
-        used += num_results ? std::min(have, num_results) : have;
-        hit_offsets[g + 1] = used;
-    }
-    if (used > cap) {
-        w->ms[2] = (now_s() - t0) * 1e3;
-        return fail(COBS_GPU_ERR_CAPACITY, "result buffer too small; hit_offsets[n_groups] holds the needed size");
-    }
-    for (size_t g = 0; g < n_groups; ++g) {
-        const GroupRec* r = recs.data() + first[g];
-        cobs_gpu_group_hit* out = hits + hit_offsets[g];
-        for (size_t i = 0, n = hit_offsets[g + 1] - hit_offsets[g]; i < n; ++i)
-            out[i] = cobs_gpu_group_hit{r[i].file, r[i].doc, r[i].sum, r[i].votes};
-    }
+    const cobs_gpu_status handed = hand_out_lists(recs, n_groups, [](const GroupRec& r) { return r.group; },
+        [](const GroupRec& a, const GroupRec& b) {
+            if (a.sum != b.sum) return a.sum > b.sum;
+            if (a.file != b.file) return a.file < b.file;
+            return a.doc < b.doc;
+        }, num_results, hits, cap, hit_offsets, "n_groups",
+        [](const GroupRec& r) { return cobs_gpu_group_hit{r.file, r.doc, r.sum, r.votes}; });
     w->ms[2] = (now_s() - t0) * 1e3;
-    return COBS_GPU_OK;
+    return handed;
 }
 
 }  // namespace

@@ -1,14 +1,15 @@
 // cobs_amd/csrc/hash_pass.cpp -- what every call that runs K1 on its own shares (declared in engine.hpp): the scratch
 // batch of the host-buffer calls, the HashArgs of a file and K1's launch per file, the TableRef a reader of K1's table
 // gets (row_table.hpp), the decode of K1's "invalid base" flag word with the reference's message, the length refusals
-// with the reference's wording, the table bytes the passes are cut by, and the prevalence cells both cobs_gpu_prevalence
-// and cobs_gpu_search_weighted fill.
+// with the reference's wording, the table bytes the passes are cut by, the prevalence cells both cobs_gpu_prevalence
+// and cobs_gpu_search_weighted fill, and the bodies of pooled_pass.hpp that are no templates.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
 #include <string>
 
 #include "engine.hpp"
+#include "pooled_pass.hpp"
 #include "prevalence_kernels.hpp"
 
 namespace cobs_amd {
@@ -128,9 +129,7 @@ cobs_gpu_status launch_prevalence_cells(cobs_gpu_index* ix, const cobs_gpu_batch
     const size_t nf = ix->parts.size();
     HIP_TRY(launch_prevalence_zero(cells, ncells, stream));
     HIP_TRY(hipEventRecord(started, stream));
-    if (cobs_gpu_status s = launch_hash_files(ix, b, n, z, stream, [&](size_t f) { return ix->parts[f].num_tpages() != 0; });
-        s != COBS_GPU_OK)
-        return s;
+    if (cobs_gpu_status s = launch_hash_held(ix, b, n, z, stream); s != COBS_GPU_OK) return s;
     HIP_TRY(hipEventRecord(hashed, stream));
     for (size_t f = 0; f < nf; ++f) {
         const Part& p = ix->parts[f];
@@ -152,5 +151,49 @@ cobs_gpu_status launch_prevalence_cells(cobs_gpu_index* ix, const cobs_gpu_batch
     }
     return COBS_GPU_OK;
 }
+
+// ---- pooled_pass.hpp
+
+cobs_gpu_status launch_hash_held(cobs_gpu_index* ix, const cobs_gpu_batch* b, size_t n, uint32_t z, hipStream_t st) {
+    return launch_hash_files(ix, b, n, z, st, [&](size_t f) { return ix->parts[f].num_tpages() != 0; });
+}
+
+cobs_gpu_status pass_queries(cobs_gpu_index* ix, const char* const* queries, const size_t* lens, size_t q0, size_t q1,
+                             size_t* bad_query, cobs_gpu_batch** b) {
+    if (cobs_gpu_status s = scratch_batch(ix, 0, b); s != COBS_GPU_OK) return s;
+    const size_t n = q1 - q0;
+    size_t bad_local = 0;
+    cobs_gpu_status s = set_queries_on(*b, queries + q0, lens + q0, n, (*b)->own_stream, false, &bad_local, q0);
+    if (s != COBS_GPU_OK && bad_query && bad_local < n) *bad_query = q0 + bad_local;
+    return s;
+}
+
+cobs_gpu_status scan_pool_no_room(uint64_t cap) {
+    return fail(COBS_GPU_ERR_HIP, "out of device memory for " + std::to_string(cap) + " hit records; raise the threshold or use fewer queries per call");
+}
+
+cobs_gpu_status hand_out_hits(std::vector<HitDev>& recs, size_t nq, size_t num_results, cobs_gpu_hit* hits, size_t cap, size_t* hit_offsets) {
+    return hand_out_lists(recs, nq, [](const HitDev& r) { return r.query; },
+        [](const HitDev& a, const HitDev& b) {
+            if (a.score != b.score) return a.score > b.score;
+            if (a.part != b.part) return a.part < b.part;
+            return a.doc < b.doc;
+        }, num_results, hits, cap, hit_offsets, "nq", [](const HitDev& r) { return cobs_gpu_hit{r.part, r.doc, r.score}; });
+}
+
+cobs_gpu_status take_ms(const cobs_gpu_index* ix, double* out, int n, double* ms, uint64_t* passes) {
+    if (!ix || !out) return fail(COBS_GPU_ERR_ARG, "NULL argument");
+    for (int i = 0; i <= n; ++i) out[i] = 0;
+    if (!ms) return COBS_GPU_OK;
+    for (int i = 0; i < n; ++i) {
+        out[i] = ms[i];
+        ms[i] = 0;
+    }
+    out[n] = (double)*passes;
+    *passes = 0;
+    return COBS_GPU_OK;
+}
+
+ScanWork::ScanWork(const char* pool_name) : hits(pool_name, launch_prevalence_zero) {}
 
 }  // namespace cobs_amd

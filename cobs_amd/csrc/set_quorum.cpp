@@ -5,8 +5,8 @@
 // them, kept per file beside the labels and dropped with them.  Per device pass (cut by the workspace limit, on the handle's
 // scratch batch): K1 hashes the queries, a kernel zeroes the cells [query][file][set][n], the count kernel adds the members
 // up, and -- for the search -- the select kernel forms core and any per (query, set) and appends the sets that reach the
-// threshold to a pool; the host orders every query's records.  cobs_gpu_set_prevalence copies the cells out instead: they
-// lie in the caller's layout.
+// threshold to a pool; the host orders every query's records (pooled_call.hpp: cut_passes, hand_out_lists).
+// cobs_gpu_set_prevalence copies the cells out instead: they lie in the caller's layout.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -115,14 +115,9 @@ cobs_gpu_status run_pass(const Call& c, size_t q0, size_t q1, uint64_t cell0) {
     HIP_TRY(hipSetDevice(ix->device));
     HIP_TRY(w->ev.create());
     cobs_gpu_batch* b = nullptr;
-    if (cobs_gpu_status s = scratch_batch(ix, 0, &b); s != COBS_GPU_OK) return s;
+    if (cobs_gpu_status s = pass_queries(ix, c.queries, c.lens, q0, q1, c.bad_query, &b); s != COBS_GPU_OK) return s;
     hipStream_t st = b->own_stream;
     const size_t n = q1 - q0, nf = ix->parts.size(), nitems = c.items ? c.items->size() : 0;
-    size_t bad_local = 0;
-    if (cobs_gpu_status s = set_queries_on(b, c.queries + q0, c.lens + q0, n, st, false, &bad_local, q0); s != COBS_GPU_OK) {
-        if (c.bad_query && bad_local < n) *c.bad_query = q0 + bad_local;
-        return s;
-    }
     // the cells of the pass: per (query, file) its sets' counts back to back, set-major
     HIP_TRY(w->cell_off.reserve(n * nf + 1));
     HIP_TRY(w->h_cell_off.reserve(n * nf + 1));
@@ -143,7 +138,7 @@ cobs_gpu_status run_pass(const Call& c, size_t q0, size_t q1, uint64_t cell0) {
                     " queries; lower pass_bytes or use fewer queries per call");
     }
     HIP_TRY(w->fill.reserve(1));
-    HIP_TRY(w->h_flags.reserve(6));
+    HIP_TRY(w->land.reserve());
     const bool count_valid = ix->invalid_bases == COBS_GPU_INVALID_SKIP;
 
     HIP_TRY(hipMemcpyAsync(w->cell_off.p, w->h_cell_off.p, (n * nf + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
@@ -202,22 +197,16 @@ cobs_gpu_status run_pass(const Call& c, size_t q0, size_t q1, uint64_t cell0) {
         HIP_TRY(launch_set_quorum_select(sa, st));
     }
     HIP_TRY(w->ev.mark(3, st));
-    HIP_TRY(hipMemcpyAsync(w->h_flags.p, b->flags.p, 16, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(w->h_flags.p + 4, w->fill.p, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(w->land.flags_home(b, st));
+    HIP_TRY(w->land.fill_home(w->fill.p, st));
     if (c.counts && cells) HIP_TRY(hipMemcpyAsync(c.counts + cell0, w->cells.p, (size_t)cells * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (w->ev.add_elapsed(w->ms)) w->passes++;
-    if (cobs_gpu_status s = invalid_base_from_flags(w->h_flags.p[0], n, c.bad_query, q0); s != COBS_GPU_OK) return s;
+    if (cobs_gpu_status s = invalid_base_from_flags(w->land.invalid_word(), n, c.bad_query, q0); s != COBS_GPU_OK) return s;
     if (!c.items) return COBS_GPU_OK;
-    const uint64_t fill = (uint64_t)w->h_flags.p[5] << 32 | w->h_flags.p[4];
+    const uint64_t fill = w->land.fill();
     if (fill > pool_cap) return fail(COBS_GPU_ERR_HIP, "set quorum: the record pool overflowed");      // (it holds every item)
-    const size_t at = c.recs->size();
-    c.recs->resize(at + (size_t)fill);
-    if (fill) {
-        HIP_TRY(hipMemcpy(c.recs->data() + at, w->pool.p, (size_t)fill * sizeof(SetQuorumRec), hipMemcpyDeviceToHost));
-        for (size_t i = at; i < c.recs->size(); ++i) (*c.recs)[i].query += (uint32_t)q0;
-    }
-    return COBS_GPU_OK;
+    return append_pass_records(*c.recs, w->pool.p, fill, q0);
 }
 
 // what both calls refuse on the handle and the queries, before anything is launched
@@ -251,20 +240,12 @@ cobs_gpu_status run_passes(const Call& call, size_t nq, size_t rec_bytes_per_que
         qbytes[q] = (uint64_t)(call.lens[q] + 16) * terms_per_char + cb;
     }
     if (cobs_gpu_status s = ensure_runs(ix, call.w); s != COBS_GPU_OK) return s;
-    size_t first = 0;
-    uint64_t bytes = 0, cell0 = 0, cells = 0;
-    for (size_t q = 0; q < nq; ++q) {
-        if (q > first && bytes + qbytes[q] > kLimit) {
-            if (cobs_gpu_status s = run_pass(call, first, q, cell0); s != COBS_GPU_OK) return s;
-            first = q;
-            bytes = 0;
-            cell0 += cells;
-            cells = 0;
-        }
-        bytes += qbytes[q];
-        cells += qcells[q];
-    }
-    return run_pass(call, first, nq, cell0);
+    uint64_t cell0 = 0;
+    return cut_passes(nq, kLimit, [&](size_t q) { return qbytes[q]; }, [&](size_t q0, size_t q1) {
+        const uint64_t at = cell0;
+        for (size_t q = q0; q < q1; ++q) cell0 += qcells[q];
+        return run_pass(call, q0, q1, at);
+    });
 }
 
 cobs_gpu_status search_sets_quorum_impl(cobs_gpu_index* ix, const char* const* queries, const size_t* lens, size_t nq,
@@ -309,33 +290,15 @@ cobs_gpu_status search_sets_quorum_impl(cobs_gpu_index* ix, const char* const* q
     // ---- ordering: per query by core descending, then any descending, then (file, set) ascending -- the items are in
     // (file, set) order --; num_results cuts the list
     const double t0 = now_s();
-    std::sort(recs.begin(), recs.end(), [](const SetQuorumRec& a, const SetQuorumRec& b) {
-        if (a.query != b.query) return a.query < b.query;
-        if (a.core != b.core) return a.core > b.core;
-        if (a.any != b.any) return a.any > b.any;
-        return a.item < b.item;
-    });
-    std::vector<size_t> begin(nq + 1, 0);
-    for (const SetQuorumRec& r : recs) begin[r.query + 1]++;
-    for (size_t q = 0; q < nq; ++q) begin[q + 1] += begin[q];
-    size_t used = 0;
-    for (size_t q = 0; q < nq; ++q) {
-        const size_t have = begin[q + 1] - begin[q];
-        used += num_results ? std::min(have, num_results) : have;
-        hit_offsets[q + 1] = used;
-    }
-    if (used > cap) {
-        w->quorum.ms[3] += (now_s() - t0) * 1e3;
-        return fail(COBS_GPU_ERR_CAPACITY, "result buffer too small; hit_offsets[nq] holds the needed size");
-    }
-    for (size_t q = 0; q < nq; ++q) {
-        const SetQuorumRec* r = recs.data() + begin[q];
-        cobs_gpu_set_quorum_hit* out = hits + hit_offsets[q];
-        for (size_t i = 0, n = hit_offsets[q + 1] - hit_offsets[q]; i < n; ++i)
-            out[i] = cobs_gpu_set_quorum_hit{items[r[i].item].file_no, items[r[i].item].set, r[i].core, r[i].any};
-    }
+    const cobs_gpu_status handed = hand_out_lists(recs, nq, [](const SetQuorumRec& r) { return r.query; },
+        [](const SetQuorumRec& a, const SetQuorumRec& b) {
+            if (a.core != b.core) return a.core > b.core;
+            if (a.any != b.any) return a.any > b.any;
+            return a.item < b.item;
+        }, num_results, hits, cap, hit_offsets, "nq",
+        [&](const SetQuorumRec& r) { return cobs_gpu_set_quorum_hit{items[r.item].file_no, items[r.item].set, r.core, r.any}; });
     w->quorum.ms[3] += (now_s() - t0) * 1e3;
-    return COBS_GPU_OK;
+    return handed;
 }
 
 cobs_gpu_status set_prevalence_impl(cobs_gpu_index* ix, const char* const* queries, const size_t* lens, size_t nq,
@@ -384,17 +347,8 @@ cobs_gpu_status cobs_gpu_set_prevalence(cobs_gpu_index* ix, const char* const* q
 }
 
 cobs_gpu_status cobs_gpu_set_quorum_ms(cobs_gpu_index* ix, double out[5]) {
-    if (!ix || !out) return fail(COBS_GPU_ERR_ARG, "NULL argument");
-    for (int i = 0; i < 5; ++i) out[i] = 0;
-    if (SetsWork* w = ix->sets) {
-        for (int i = 0; i < 4; ++i) {
-            out[i] = w->quorum.ms[i];
-            w->quorum.ms[i] = 0;
-        }
-        out[4] = (double)w->quorum.passes;
-        w->quorum.passes = 0;
-    }
-    return COBS_GPU_OK;
+    SetsWork* w = ix ? ix->sets : nullptr;
+    return take_ms(ix, out, 4, w ? w->quorum.ms : nullptr, w ? &w->quorum.passes : nullptr);
 }
 
 }  // extern "C"

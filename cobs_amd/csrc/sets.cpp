@@ -5,7 +5,7 @@
 // the workspace limit, on the handle's scratch batch): K1 hashes the queries (unchanged: findere and the invalid-bases
 // policy live in its table), the presence kernel ORs the two bit matrices [query][set][ceil(n / 32)] together, the select
 // kernel counts their bits and appends the sets that reach the threshold to a pool (set_kernels.hip).  The host orders
-// every query's records and cuts them to num_results, as groups.cpp does for its groups.
+// every query's records and cuts them to num_results (pooled_call.hpp: cut_passes, hand_out_lists).
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -140,14 +140,9 @@ cobs_gpu_status run_pass(const Call& c, size_t q0, size_t q1) {
     HIP_TRY(hipSetDevice(ix->device));
     HIP_TRY(w->ev.create());
     cobs_gpu_batch* b = nullptr;
-    if (cobs_gpu_status s = scratch_batch(ix, 0, &b); s != COBS_GPU_OK) return s;
+    if (cobs_gpu_status s = pass_queries(ix, c.queries, c.lens, q0, q1, c.bad_query, &b); s != COBS_GPU_OK) return s;
     hipStream_t st = b->own_stream;
     const size_t n = q1 - q0, nf = ix->parts.size(), nitems = c.items->size();
-    size_t bad_local = 0;
-    if (cobs_gpu_status s = set_queries_on(b, c.queries + q0, c.lens + q0, n, st, false, &bad_local, q0); s != COBS_GPU_OK) {
-        if (c.bad_query && bad_local < n) *c.bad_query = q0 + bad_local;
-        return s;
-    }
     // the bitmaps of the pass: per (query, file) its sets' words back to back; `miss` lies `words` behind `any`
     HIP_TRY(w->bm_off.reserve(n * nf + 1));
     HIP_TRY(w->h_bm_off.reserve(n * nf + 1));
@@ -168,7 +163,7 @@ cobs_gpu_status run_pass(const Call& c, size_t q0, size_t q1) {
                     " queries; lower pass_bytes or use fewer queries per call");
     }
     HIP_TRY(w->fill.reserve(1));
-    HIP_TRY(w->h_flags.reserve(6));
+    HIP_TRY(w->land.reserve());
     const bool count_valid = ix->invalid_bases == COBS_GPU_INVALID_SKIP;
 
     HIP_TRY(hipMemcpyAsync(w->bm_off.p, w->h_bm_off.p, (n * nf + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
@@ -229,20 +224,14 @@ cobs_gpu_status run_pass(const Call& c, size_t q0, size_t q1) {
     sa.rank_by = c.rank_by;
     HIP_TRY(launch_set_select(sa, st));
     HIP_TRY(w->ev.mark(3, st));
-    HIP_TRY(hipMemcpyAsync(w->h_flags.p, b->flags.p, 16, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(w->h_flags.p + 4, w->fill.p, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(w->land.flags_home(b, st));
+    HIP_TRY(w->land.fill_home(w->fill.p, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (w->ev.add_elapsed(w->ms)) w->passes++;
-    if (cobs_gpu_status s = invalid_base_from_flags(w->h_flags.p[0], n, c.bad_query, q0); s != COBS_GPU_OK) return s;
-    const uint64_t fill = (uint64_t)w->h_flags.p[5] << 32 | w->h_flags.p[4];
+    if (cobs_gpu_status s = invalid_base_from_flags(w->land.invalid_word(), n, c.bad_query, q0); s != COBS_GPU_OK) return s;
+    const uint64_t fill = w->land.fill();
     if (fill > pool_cap) return fail(COBS_GPU_ERR_HIP, "sets: the record pool overflowed");      // (it holds every item)
-    const size_t at = c.recs->size();
-    c.recs->resize(at + (size_t)fill);
-    if (fill) {
-        HIP_TRY(hipMemcpy(c.recs->data() + at, w->pool.p, (size_t)fill * sizeof(SetRec), hipMemcpyDeviceToHost));
-        for (size_t i = at; i < c.recs->size(); ++i) (*c.recs)[i].query += (uint32_t)q0;
-    }
-    return COBS_GPU_OK;
+    return append_pass_records(*c.recs, w->pool.p, fill, q0);
 }
 
 cobs_gpu_status search_sets_impl(cobs_gpu_index* ix, const char* const* queries, const size_t* lens, size_t nq, double threshold,
@@ -299,51 +288,25 @@ cobs_gpu_status search_sets_impl(cobs_gpu_index* ix, const char* const* queries,
         HIP_TRY(w->items.reserve(items.size()));
         HIP_TRY(hipMemcpy(w->items.p, items.data(), items.size() * sizeof(SetItem), hipMemcpyHostToDevice));
     }
-    size_t first = 0;
-    uint64_t bytes = 0;
-    for (size_t q = 0; q < nq; ++q) {
-        if (q > first && bytes + qbytes[q] > kLimit) {
-            if (cobs_gpu_status s = run_pass(call, first, q); s != COBS_GPU_OK) return s;
-            first = q;
-            bytes = 0;
-        }
-        bytes += qbytes[q];
-    }
-    if (cobs_gpu_status s = run_pass(call, first, nq); s != COBS_GPU_OK) return s;
+    if (cobs_gpu_status s = cut_passes(nq, kLimit, [&](size_t q) { return qbytes[q]; }, [&](size_t q0, size_t q1) { return run_pass(call, q0, q1); });
+        s != COBS_GPU_OK)
+        return s;
 
     // ---- ordering: per query by the key descending, then the other count descending, then (file, set) ascending -- the
     // items are in (file, set) order --; num_results cuts the list
     const double t0 = now_s();
     const bool by_all = rank_by == COBS_GPU_SETS_BY_ALL;
-    std::sort(recs.begin(), recs.end(), [by_all](const SetRec& a, const SetRec& b) {
-        if (a.query != b.query) return a.query < b.query;
-        const uint32_t ka = by_all ? a.all : a.any, kb = by_all ? b.all : b.any;
-        if (ka != kb) return ka > kb;
-        const uint32_t oa = by_all ? a.any : a.all, ob = by_all ? b.any : b.all;
-        if (oa != ob) return oa > ob;
-        return a.item < b.item;
-    });
-    std::vector<size_t> begin(nq + 1, 0);
-    for (const SetRec& r : recs) begin[r.query + 1]++;
-    for (size_t q = 0; q < nq; ++q) begin[q + 1] += begin[q];
-    size_t used = 0;
-    for (size_t q = 0; q < nq; ++q) {
-        const size_t have = begin[q + 1] - begin[q];
-        used += num_results ? std::min(have, num_results) : have;
-        hit_offsets[q + 1] = used;
-    }
-    if (used > cap) {
-        w->ms[3] += (now_s() - t0) * 1e3;
-        return fail(COBS_GPU_ERR_CAPACITY, "result buffer too small; hit_offsets[nq] holds the needed size");
-    }
-    for (size_t q = 0; q < nq; ++q) {
-        const SetRec* r = recs.data() + begin[q];
-        cobs_gpu_set_hit* out = hits + hit_offsets[q];
-        for (size_t i = 0, n = hit_offsets[q + 1] - hit_offsets[q]; i < n; ++i)
-            out[i] = cobs_gpu_set_hit{items[r[i].item].file_no, items[r[i].item].set, r[i].any, r[i].all};
-    }
+    const cobs_gpu_status handed = hand_out_lists(recs, nq, [](const SetRec& r) { return r.query; },
+        [by_all](const SetRec& a, const SetRec& b) {
+            const uint32_t ka = by_all ? a.all : a.any, kb = by_all ? b.all : b.any;
+            if (ka != kb) return ka > kb;
+            const uint32_t oa = by_all ? a.any : a.all, ob = by_all ? b.any : b.all;
+            if (oa != ob) return oa > ob;
+            return a.item < b.item;
+        }, num_results, hits, cap, hit_offsets, "nq",
+        [&](const SetRec& r) { return cobs_gpu_set_hit{items[r.item].file_no, items[r.item].set, r.any, r.all}; });
     w->ms[3] += (now_s() - t0) * 1e3;
-    return COBS_GPU_OK;
+    return handed;
 }
 
 }  // namespace
@@ -380,17 +343,8 @@ cobs_gpu_status cobs_gpu_search_sets(cobs_gpu_index* ix, const char* const* quer
 }
 
 cobs_gpu_status cobs_gpu_sets_ms(cobs_gpu_index* ix, double out[5]) {
-    if (!ix || !out) return fail(COBS_GPU_ERR_ARG, "NULL argument");
-    for (int i = 0; i < 5; ++i) out[i] = 0;
-    if (SetsWork* w = ix->sets) {
-        for (int i = 0; i < 4; ++i) {
-            out[i] = w->ms[i];
-            w->ms[i] = 0;
-        }
-        out[4] = (double)w->passes;
-        w->passes = 0;
-    }
-    return COBS_GPU_OK;
+    SetsWork* w = ix ? ix->sets : nullptr;
+    return take_ms(ix, out, 4, w ? w->ms : nullptr, w ? &w->passes : nullptr);
 }
 
 }  // extern "C"

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "engine.hpp"
+#include "pooled_pass.hpp"
 #include "set_count_kernels.hpp"
 #include "set_kernels.hpp"
 
@@ -45,7 +46,7 @@ struct SetQuorumWork {                      // set_quorum.cpp
     DevBuf<SetQuorumRec> pool;
     DevBuf<unsigned long long> fill;
     PinnedBuf<uint64_t> h_cell_off;
-    PinnedBuf<uint32_t> h_flags;            // K1's flag words | the pool's 64-bit fill
+    PassLanding land;
     PhaseEvents<4> ev;                      // before K1 | count | select | after it
     double ms[4] = {0, 0, 0, 0};            // hash | count | select | host ordering
     uint64_t passes = 0;
@@ -59,7 +60,7 @@ struct SetsWork {
     DevBuf<SetRec> pool;
     DevBuf<unsigned long long> fill;
     PinnedBuf<uint64_t> h_bm_off;
-    PinnedBuf<uint32_t> h_flags;            // K1's flag words | the pool's 64-bit fill
+    PassLanding land;
     PhaseEvents<4> ev;                      // before K1 | presence | select | after it
     double ms[4] = {0, 0, 0, 0};            // hash | presence | select | host ordering
     uint64_t passes = 0;

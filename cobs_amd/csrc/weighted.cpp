@@ -3,8 +3,9 @@
 // (unchanged: findere and the invalid-bases policy live in its table), the prevalence kernel counts the documents of
 // every position into device cells, the weight kernel turns the cells into one byte per position plus W(q, f) and the
 // threshold of every (query, file), and the weighted scan appends the documents that reach it to a pool
-// (weighted_kernels.hip).  A pool that overflows is grown to the fill the scan reports and the scan of that pass alone
-// runs again.  The host orders every query's records and cuts them to num_results, as groups.cpp does for its groups.
+// (weighted_kernels.hip).  The pool with its retry, the pass cutter and the hand-over are the shared ones
+// (pooled_pass.hpp, pooled_call.hpp).  The pass itself stands here and not in run_scan_pass: two kernels run in front of
+// the scan, under five events, and the totals come home in the sync the flag words come home in.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -13,6 +14,7 @@
 #include <vector>
 
 #include "engine.hpp"
+#include "pooled_pass.hpp"
 #include "prevalence_kernels.hpp"
 #include "weighted_kernels.hpp"
 
@@ -23,10 +25,9 @@ struct WeightedWork {
     DevBuf<uint8_t> weights;
     DevBuf<uint64_t> seg_off, total;
     DevBuf<uint32_t> thr;                   // [file][nq]
-    DevBuf<HitDev> pool;
-    DevBuf<unsigned long long> fill;
+    HitPool<HitDev> hits{"weighted: the hit pool", launch_prevalence_zero};
     PinnedBuf<uint64_t> h_seg_off, h_total;
-    PinnedBuf<uint32_t> h_flags;            // K1's flag words | the pool's 64-bit fill
+    PassLanding land;
     PhaseEvents<5> ev;                      // before K1 | prevalence | weights | scan | after it
     double ms[4] = {0, 0, 0, 0};            // hash | prevalence | weights | scan
     uint64_t passes = 0;
@@ -36,16 +37,8 @@ void destroy_weighted_work(WeightedWork* w) { delete w; }
 
 namespace {
 
-struct Call {
-    cobs_gpu_index* ix;
-    const char* const* queries;
-    const size_t* lens;
-    double threshold;
+struct Call : ScanCall {
     uint64_t* total_weight;
-    size_t* bad_query;
-    uint32_t z;
-    uint64_t real_total;                    // real documents of all files
-    std::vector<HitDev>* recs;              // the records of all passes, `query` = the call's query number
 };
 
 // the scan of the pass's queries over every resident chunk, into the pool
@@ -60,8 +53,8 @@ cobs_gpu_status launch_scans(const Call& c, WeightedWork* w, cobs_gpu_batch* b, 
         sa.seg_off = w->seg_off.p + f;
         sa.weights = w->weights.p;
         sa.thr = w->thr.p + f * n;
-        sa.pool = w->pool.p;
-        sa.fill = w->fill.p;
+        sa.pool = w->hits.pool.p;
+        sa.fill = w->hits.fill.p;
         sa.cap = pool_cap;
         sa.seg_stride = (uint32_t)nf;
         sa.nq = (uint32_t)n;
@@ -91,14 +84,9 @@ cobs_gpu_status run_pass(const Call& c, size_t q0, size_t q1) {
     WeightedWork* w = ix->weighted;
     HIP_TRY(w->ev.create());
     cobs_gpu_batch* b = nullptr;
-    if (cobs_gpu_status s = scratch_batch(ix, 0, &b); s != COBS_GPU_OK) return s;
+    if (cobs_gpu_status s = pass_queries(ix, c.queries, c.lens, q0, q1, c.bad_query, &b); s != COBS_GPU_OK) return s;
     hipStream_t st = b->own_stream;
     const size_t n = q1 - q0, nf = ix->parts.size();
-    size_t bad_local = 0;
-    if (cobs_gpu_status s = set_queries_on(b, c.queries + q0, c.lens + q0, n, st, false, &bad_local, q0); s != COBS_GPU_OK) {
-        if (c.bad_query && bad_local < n) *c.bad_query = q0 + bad_local;
-        return s;
-    }
     // the cells of the pass: one segment per (query, file), each padded to a multiple of 8 -- the scan reads the eight
     // weights of a block with one aligned load, the padding weighs 0
     HIP_TRY(w->seg_off.reserve(n * nf + 1));
@@ -118,79 +106,57 @@ cobs_gpu_status run_pass(const Call& c, size_t q0, size_t q1) {
     HIP_TRY(w->total.reserve(n * nf));
     HIP_TRY(w->h_total.reserve(n * nf));
     HIP_TRY(w->thr.reserve(n * nf));
-    HIP_TRY(w->fill.reserve(1));
-    HIP_TRY(w->h_flags.reserve(6));
-    // the first guess of the pool (tuning key hit_cap: a small one, so that tests reach the overflow path)
-    const uint64_t all = c.real_total * n;
-    uint64_t pool_cap = c.threshold > 0.0 ? std::min<uint64_t>(all, std::max<uint64_t>(1u << 20, n * 1024ull)) : all;
-    if (ix->tune.hit_cap) pool_cap = std::min<uint64_t>(pool_cap, ix->tune.hit_cap);
-    pool_cap = std::max<uint64_t>(pool_cap, 1);
-    auto reserve_pool = [&]() -> cobs_gpu_status {
-        if (w->pool.reserve((size_t)pool_cap) != hipSuccess) {
-            (void)hipGetLastError();
-            // (not ERR_CAPACITY: that status promises the needed size of the CALLER's buffer in hit_offsets)
-            return fail(COBS_GPU_ERR_HIP, "out of device memory for " + std::to_string(pool_cap) + " hit records; raise the threshold or use fewer queries per call");
-        }
-        return COBS_GPU_OK;
-    };
-    if (cobs_gpu_status s = reserve_pool(); s != COBS_GPU_OK) return s;
+    HIP_TRY(w->land.reserve());
 
     HIP_TRY(hipMemcpyAsync(w->seg_off.p, w->h_seg_off.p, (n * nf + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
     HIP_TRY(launch_clear_flags(b->flags.p, st));
-    HIP_TRY(launch_prevalence_zero(reinterpret_cast<uint32_t*>(w->fill.p), 2, st));
-    // K1 and the prevalence of every position into the cells, exactly as cobs_gpu_prevalence fills its own
-    if (cobs_gpu_status s = launch_prevalence_cells(ix, b, w->seg_off.p, w->cells.p, ncells, n, max_len, c.z, st, w->ev.ev[0], w->ev.ev[1]);
-        s != COBS_GPU_OK)
-        return s;
-    HIP_TRY(w->ev.mark(2, st));
-    for (size_t f = 0; f < nf; ++f) {
-        const Part& p = ix->parts[f];
-        WeightArgs wa{};
-        wa.cells = w->cells.p;
-        wa.weights = w->weights.p;
-        wa.seg_off = w->seg_off.p + f;
-        wa.q_len = b->d_qlen;
-        wa.total = w->total.p + f;
-        wa.thr = w->thr.p + f * n;
-        wa.threshold = c.threshold;
-        wa.seg_stride = (uint32_t)nf;
-        wa.term_size = p.meta.term_size;
-        wa.findere = c.z;
-        wa.num_docs = (uint32_t)p.meta.doc_names.size();
-        HIP_TRY(launch_weights(wa, (uint32_t)n, st));
-    }
-    HIP_TRY(w->ev.mark(3, st));
-    if (cobs_gpu_status s = launch_scans(c, w, b, n, max_len, pool_cap, st); s != COBS_GPU_OK) return s;
-    HIP_TRY(w->ev.mark(4, st));
-    HIP_TRY(hipMemcpyAsync(w->h_flags.p, b->flags.p, 16, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(w->h_flags.p + 4, w->fill.p, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(w->h_total.p, w->total.p, n * nf * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (w->ev.add_elapsed(w->ms)) w->passes++;
-    if (cobs_gpu_status s = invalid_base_from_flags(w->h_flags.p[0], n, c.bad_query, q0); s != COBS_GPU_OK) return s;
-    uint64_t fill = (uint64_t)w->h_flags.p[5] << 32 | w->h_flags.p[4];
-    if (fill > pool_cap) {
-        // overflow: the pool grows to the reported fill and the scan of this pass alone runs again (cells and weights stay)
-        pool_cap = fill;
-        if (cobs_gpu_status s = reserve_pool(); s != COBS_GPU_OK) return s;
-        HIP_TRY(launch_prevalence_zero(reinterpret_cast<uint32_t*>(w->fill.p), 2, st));
-        HIP_TRY(w->ev.mark(3, st));
-        if (cobs_gpu_status s = launch_scans(c, w, b, n, max_len, pool_cap, st); s != COBS_GPU_OK) return s;
-        HIP_TRY(w->ev.mark(4, st));
-        HIP_TRY(hipMemcpyAsync(w->h_flags.p + 4, w->fill.p, 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        (void)w->ev.add_elapsed(w->ms, 3, 4);
-        fill = (uint64_t)w->h_flags.p[5] << 32 | w->h_flags.p[4];
-        if (fill > pool_cap) return fail(COBS_GPU_ERR_HIP, "weighted: the hit pool overflowed twice");
-    }
+    uint64_t fill = 0;
+    cobs_gpu_status s = w->hits.run(first_pool_cap(ix->tune.hit_cap, c.threshold, c.real_total, n), st, scan_pool_no_room,
+        [&](uint64_t pool_cap, int attempt) -> cobs_gpu_status {
+            if (attempt == 0) {         // (the retry scans alone: cells, weights and thresholds stay)
+                // K1 and the prevalence of every position into the cells, exactly as cobs_gpu_prevalence fills its own
+                if (cobs_gpu_status p = launch_prevalence_cells(ix, b, w->seg_off.p, w->cells.p, ncells, n, max_len, c.z, st, w->ev.ev[0], w->ev.ev[1]);
+                    p != COBS_GPU_OK)
+                    return p;
+                HIP_TRY(w->ev.mark(2, st));
+                for (size_t f = 0; f < nf; ++f) {
+                    const Part& p = ix->parts[f];
+                    WeightArgs wa{};
+                    wa.cells = w->cells.p;
+                    wa.weights = w->weights.p;
+                    wa.seg_off = w->seg_off.p + f;
+                    wa.q_len = b->d_qlen;
+                    wa.total = w->total.p + f;
+                    wa.thr = w->thr.p + f * n;
+                    wa.threshold = c.threshold;
+                    wa.seg_stride = (uint32_t)nf;
+                    wa.term_size = p.meta.term_size;
+                    wa.findere = c.z;
+                    wa.num_docs = (uint32_t)p.meta.doc_names.size();
+                    HIP_TRY(launch_weights(wa, (uint32_t)n, st));
+                }
+            }
+            HIP_TRY(w->ev.mark(3, st));
+            if (cobs_gpu_status k = launch_scans(c, w, b, n, max_len, pool_cap, st); k != COBS_GPU_OK) return k;
+            HIP_TRY(w->ev.mark(4, st));
+            return COBS_GPU_OK;
+        },
+        [&](int attempt, uint64_t* filled) -> cobs_gpu_status {
+            if (attempt == 0) HIP_TRY(w->land.flags_home(b, st));
+            HIP_TRY(w->land.fill_home(w->hits.fill.p, st));
+            if (attempt == 0) HIP_TRY(hipMemcpyAsync(w->h_total.p, w->total.p, n * nf * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            *filled = w->land.fill();
+            if (attempt != 0) {
+                (void)w->ev.add_elapsed(w->ms, 3, 4);
+                return COBS_GPU_OK;
+            }
+            if (w->ev.add_elapsed(w->ms)) w->passes++;
+            return invalid_base_from_flags(w->land.invalid_word(), n, c.bad_query, q0);
+        }, &fill);
+    if (s != COBS_GPU_OK) return s;
     if (c.total_weight) std::memcpy(c.total_weight + q0 * nf, w->h_total.p, n * nf * sizeof(uint64_t));
-    const size_t at = c.recs->size();
-    c.recs->resize(at + (size_t)fill);
-    if (fill) {
-        HIP_TRY(hipMemcpy(c.recs->data() + at, w->pool.p, (size_t)fill * sizeof(HitDev), hipMemcpyDeviceToHost));
-        for (size_t i = at; i < c.recs->size(); ++i) (*c.recs)[i].query += (uint32_t)q0;
-    }
-    return COBS_GPU_OK;
+    return append_pass_records(*c.recs, w->hits.pool.p, fill, q0);
 }
 
 cobs_gpu_status search_weighted_impl(cobs_gpu_index* ix, const char* const* queries, const size_t* lens, size_t nq,
@@ -218,55 +184,21 @@ cobs_gpu_status search_weighted_impl(cobs_gpu_index* ix, const char* const* quer
     if (total_weight) std::fill(total_weight, total_weight + nq * nf, 0ull);
     if (nq == 0 || nf == 0) return COBS_GPU_OK;
 
-    uint64_t real_total = 0;
-    for (const Part& p : ix->parts) {
-        const uint64_t docs = p.meta.doc_names.size();
-        real_total += docs > p.slot_begin ? std::min<uint64_t>(docs - p.slot_begin, p.slot_count) : 0;
-    }
     std::vector<HitDev> recs;
-    const Call call{ix, queries, lens, threshold, total_weight, bad_query, z, real_total, &recs};
+    const Call call{{ix, queries, lens, threshold, bad_query, z, real_documents(*ix), &recs}, total_weight};
     // passes: K1's tables, 5 bytes per position and file, and -- when every document comes back -- the pool's records stay
     // below the search call's workspace limit
-    const uint64_t kLimit = ix->tune.pass_bytes;
     const uint64_t terms_per_char = table_bytes_per_char(ix);
-    const uint64_t pool_bytes = threshold > 0.0 ? 0 : real_total * sizeof(HitDev);
-    size_t first = 0;
-    uint64_t bytes = 0;
-    for (size_t q = 0; q < nq; ++q) {
-        uint64_t qb = (uint64_t)(lens[q] + 16) * terms_per_char + pool_bytes;
-        for (const Part& p : ix->parts) qb += 5ull * round_up(lens[q] - p.meta.term_size + 1 - z, 8);
-        if (q > first && bytes + qb > kLimit) {
-            if (cobs_gpu_status s = run_pass(call, first, q); s != COBS_GPU_OK) return s;
-            first = q;
-            bytes = 0;
-        }
-        bytes += qb;
-    }
-    if (cobs_gpu_status s = run_pass(call, first, nq); s != COBS_GPU_OK) return s;
-
-    // ---- ordering: per query by score descending, then (file, document) ascending; num_results cuts the list
-    std::sort(recs.begin(), recs.end(), [](const HitDev& a, const HitDev& b) {
-        if (a.query != b.query) return a.query < b.query;
-        if (a.score != b.score) return a.score > b.score;
-        if (a.part != b.part) return a.part < b.part;
-        return a.doc < b.doc;
-    });
-    std::vector<size_t> begin(nq + 1, 0);
-    for (const HitDev& r : recs) begin[r.query + 1]++;
-    for (size_t q = 0; q < nq; ++q) begin[q + 1] += begin[q];
-    size_t used = 0;
-    for (size_t q = 0; q < nq; ++q) {
-        const size_t have = begin[q + 1] - begin[q];
-        used += num_results ? std::min(have, num_results) : have;
-        hit_offsets[q + 1] = used;
-    }
-    if (used > cap) return fail(COBS_GPU_ERR_CAPACITY, "result buffer too small; hit_offsets[nq] holds the needed size");
-    for (size_t q = 0; q < nq; ++q) {
-        const HitDev* r = recs.data() + begin[q];
-        cobs_gpu_hit* out = hits + hit_offsets[q];
-        for (size_t i = 0, n = hit_offsets[q + 1] - hit_offsets[q]; i < n; ++i) out[i] = cobs_gpu_hit{r[i].part, r[i].doc, r[i].score};
-    }
-    return COBS_GPU_OK;
+    const uint64_t pool_bytes = threshold > 0.0 ? 0 : call.real_total * sizeof(HitDev);
+    cobs_gpu_status s = cut_passes(nq, ix->tune.pass_bytes,
+        [&](size_t q) {
+            uint64_t qb = (uint64_t)(lens[q] + 16) * terms_per_char + pool_bytes;
+            for (const Part& p : ix->parts) qb += 5ull * round_up(lens[q] - p.meta.term_size + 1 - z, 8);
+            return qb;
+        },
+        [&](size_t q0, size_t q1) { return run_pass(call, q0, q1); });
+    if (s != COBS_GPU_OK) return s;
+    return hand_out_hits(recs, nq, num_results, hits, cap, hit_offsets);
 }
 
 }  // namespace
@@ -287,17 +219,8 @@ cobs_gpu_status cobs_gpu_search_weighted(cobs_gpu_index* ix, const char* const* 
 }
 
 cobs_gpu_status cobs_gpu_weighted_ms(cobs_gpu_index* ix, double out[5]) {
-    if (!ix || !out) return fail(COBS_GPU_ERR_ARG, "NULL argument");
-    for (int i = 0; i < 5; ++i) out[i] = 0;
-    if (WeightedWork* w = ix->weighted) {
-        for (int i = 0; i < 4; ++i) {
-            out[i] = w->ms[i];
-            w->ms[i] = 0;
-        }
-        out[4] = (double)w->passes;
-        w->passes = 0;
-    }
-    return COBS_GPU_OK;
+    WeightedWork* w = ix ? ix->weighted : nullptr;
+    return take_ms(ix, out, 4, w ? w->ms : nullptr, w ? &w->passes : nullptr);
 }
 
 }  // extern "C"
