@@ -227,6 +227,7 @@ SYMBOLS = {
     "cobs_gpu_batch_score_histogram": (_int, [_vp, _pu64, _sz]),
     "cobs_gpu_batch_hits_host": (_int, [_vp, _sz, _sz, C.POINTER(Hit), _sz, C.POINTER(_sz)]),
     "cobs_gpu_batch_stats": (_int, [_vp, C.POINTER(_u64 * 4)]),
+    "cobs_gpu_batch_scan_geometry": (_int, [_vp, C.POINTER(_u32 * 4)]),
     "cobs_gpu_batch_kernel_ms": (_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "cobs_gpu_batch_phase_stamps": (_int, [_vp, _pu64, _sz, C.POINTER(_sz)]),
     "cobs_gpu_multi_open": (_int, [C.POINTER(_cp), _sz, C.POINTER(_int), _sz, C.POINTER(Options), C.POINTER(_vp)]),

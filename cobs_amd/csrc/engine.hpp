@@ -441,6 +441,7 @@ struct cobs_gpu_batch {
     size_t res_topk = 0, res_pool = 0, res_pool_n = 0;
     bool res_rows = false;            // ... and the score rows of an all-documents pass, into h_rows
     bool self_hash_run = false;       // the last run_impl took the self-hashing form
+    uint32_t last_geom[4] = {0, 0, 0, 0};   // tile width, waves, multi-query, LDS-staged of its last scan launch (diagnostics)
     bool graph_self_hash = false;     // ... and so did the run the current graph was captured from (diagnostics)
     // shapes captured earlier (a service sees a handful of read lengths, not one): the current graph
     // above plus a few older ones, least recently used first to go; and the keys of shapes seen once

@@ -864,6 +864,10 @@ cobs_gpu_status cobs_amd::run_impl(cobs_gpu_batch* b, double threshold, size_t t
                 sa.dbg_every = (uint32_t)std::max<uint64_t>(1, groups / sa.dbg_slots);
             }
             HIP_TRY(launch_scan(sa, ntiles, b->planes, nwaves, geom.multi_query, (b->max_terms + 7) / 8, st));
+            b->last_geom[0] = sa.tile_w;         // (diagnostics: cobs_gpu_batch_scan_geometry)
+            b->last_geom[1] = (uint32_t)nwaves;
+            b->last_geom[2] = geom.multi_query ? 1u : 0u;
+            b->last_geom[3] = sa.lds_staged;
             if (!acc_mode) tile_base += ntiles;
             ++launches;
             if (partial) {
@@ -1047,6 +1051,12 @@ cobs_gpu_status cobs_gpu_batch_phase_stamps(cobs_gpu_batch* b, uint64_t* out, si
 cobs_gpu_status cobs_gpu_batch_stats(const cobs_gpu_batch* b, uint64_t out[4]) {
     if (!b || !out) return fail(COBS_GPU_ERR_ARG, "NULL argument");
     std::memcpy(out, b->stats, sizeof b->stats);
+    return COBS_GPU_OK;
+}
+
+cobs_gpu_status cobs_gpu_batch_scan_geometry(const cobs_gpu_batch* b, uint32_t out[4]) {
+    if (!b || !out) return fail(COBS_GPU_ERR_ARG, "NULL argument");
+    std::memcpy(out, b->last_geom, sizeof b->last_geom);
     return COBS_GPU_OK;
 }
 

@@ -1714,6 +1714,12 @@ class Batch:
         return {"algorithmic_bytes": int(s[0]), "scan_launches": int(s[1]), "kmer_lookups": int(s[2]),
                 "table_bytes": int(s[3])}
 
+    def scan_geometry(self):
+        """the launch geometry of the last scan launch outside a replayed graph (diagnostics)"""
+        g = (C.c_uint32 * 4)()
+        check(self._lib.cobs_gpu_batch_scan_geometry(self._h, C.byref(g)))
+        return {"tile_w": int(g[0]), "waves": int(g[1]), "mq": bool(g[2]), "lds_staged": bool(g[3])}
+
     def kernel_ms(self):
         a, b = C.c_float(0), C.c_float(0)
         check(self._lib.cobs_gpu_batch_kernel_ms(self._h, C.byref(a), C.byref(b)))

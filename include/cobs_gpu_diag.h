@@ -75,6 +75,10 @@ cobs_gpu_status cobs_gpu_read_rows(const cobs_gpu_index* ix, size_t file_no, uin
  *          a run of the same batch on the table path use it --, so this is traffic,
  *          not footprint.                                                          */
 cobs_gpu_status cobs_gpu_batch_stats(const cobs_gpu_batch* b, uint64_t out[4]);
+/* The launch geometry of the last scan-kernel launch of the batch that ran outside a replayed graph: out[0] = tile width
+ * in 16-byte chunks, out[1] = waves per work-group, out[2] = 1 for the multi-query form, out[3] = 1 for the LDS-staged
+ * variant.  All 0 before the first launch.  Tests read it to see that a forced tuning key reached the launch. */
+cobs_gpu_status cobs_gpu_batch_scan_geometry(const cobs_gpu_batch* b, uint32_t out[4]);
 /* HIP-event duration (ms) of the scan kernel(s) / hash kernel, averaged over the
  * runs since the previous call (at most the last 64); events are recorded on the
  * stream the kernels were launched on.  Call after cobs_gpu_batch_sync. */
