@@ -240,6 +240,23 @@ def release_build_buffers():
     _capi.load().cobs_gpu_build_release_buffers()
 
 
+def last_count_table():
+    """diagnostics (cobs_gpu_last_count_table): the counting table of the last batch of the last build with
+    min_count >= 2 on the current device -> (slots, text bytes of the batch, owner words, count words) as numpy arrays,
+    or None when there is no table (no such build yet, or release_build_buffers since)"""
+    import numpy as np
+    lib = _capi.load()
+    out = (C.c_uint64 * 2)()
+    check(lib.cobs_gpu_last_count_table(C.byref(out), None, None, 0))
+    cap = int(out[0])
+    if cap == 0:
+        return None
+    owner, count = np.zeros(cap, dtype=np.uint64), np.zeros(cap, dtype=np.uint32)
+    check(lib.cobs_gpu_last_count_table(C.byref(out), owner.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                        count.ctypes.data_as(C.POINTER(C.c_uint32)), cap))
+    return int(out[0]), int(out[1]), owner, count
+
+
 def classic_combine(in_files, out_file, mem_bytes=0, device=-1):
     """classic_combine (construction/classic_index.cpp:195-327): several classic indexes with the
     same parameters -> one, rows concatenated at bit granularity on the GPU"""
@@ -279,6 +296,6 @@ def write_synthetic(out_file, kind, signature_sizes, num_docs, page_size=0, term
     check(lib.cobs_gpu_write_synthetic(C.byref(d), os.fsencode(out_file), device))
 
 
-__all__ = ["write_synthetic", "build_search", "release_build_buffers", "classic_combine", "compact_combine", "classic_construct_random", "DocumentList", "DocumentEntry", "FileType", "ClassicIndexParameters", "CompactIndexParameters",
+__all__ = ["write_synthetic", "build_search", "release_build_buffers", "last_count_table", "classic_combine", "compact_combine", "classic_construct_random", "DocumentList", "DocumentEntry", "FileType", "ClassicIndexParameters", "CompactIndexParameters",
            "classic_construct", "classic_construct_list", "compact_construct", "compact_construct_list",
            "disable_cache"]

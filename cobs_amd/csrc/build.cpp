@@ -157,6 +157,7 @@ struct BuildContext {
         a.count = reinterpret_cast<uint32_t*>(table->p + cap * 8);
         a.mask = cap - 1;
         a.total = total;
+        stage_pool().note_table(table, cap, total);
         return COBS_GPU_OK;
     }
     BuildContext() = default;
@@ -710,6 +711,29 @@ cobs_gpu_status finish_batch(StagingContext& ctx, StagedBatch& b) {
 extern "C" {
 
 void cobs_gpu_build_release_buffers(void) { stage_pool().release_idle(); }
+
+// cobs_gpu_diag.h: the counting table of the last batch that was counted with a cutoff, as the device left it.  Host
+// code only: every builder has synchronised its build stream before it returns, the buffer stays in the stage pool.
+cobs_gpu_status cobs_gpu_last_count_table(uint64_t out[2], uint64_t* owner, uint32_t* count, size_t cap_slots) {
+    if (!out) return cobs_gpu_set_error(COBS_GPU_ERR_ARG, "out is NULL");
+    out[0] = out[1] = 0;
+    StagePool& pool = stage_pool();
+    std::lock_guard<std::mutex> g(pool.mu);
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return COBS_GPU_OK; }
+    if (!pool.last_table || pool.device != dev) return COBS_GPU_OK;     // no table (never built, released, another device)
+    const uint64_t cap = pool.last_cap;
+    if (pool.last_table->cap < cap * kAbundanceSlotBytes)
+        return cobs_gpu_set_error(COBS_GPU_ERR_HIP, "the counting table is smaller than its recorded capacity");
+    out[0] = cap;
+    out[1] = pool.last_total;
+    if (!owner && !count) return COBS_GPU_OK;
+    if (cap_slots < cap) return cobs_gpu_set_error(COBS_GPU_ERR_CAPACITY, "cobs_gpu_last_count_table: buffers hold fewer slots than the table");
+    const uint8_t* p = pool.last_table->p;
+    if (owner) BUILD_TRY(hipMemcpy(owner, p, (size_t)(cap * 8), hipMemcpyDeviceToHost));
+    if (count) BUILD_TRY(hipMemcpy(count, p + cap * 8, (size_t)(cap * 4), hipMemcpyDeviceToHost));
+    return COBS_GPU_OK;
+}
 
 cobs_gpu_status cobs_gpu_build_classic(const char* const* names, const char* const* texts, const size_t* lens,
                                        size_t ndocs, const cobs_gpu_build_params* params, const char* out_path) {

@@ -103,6 +103,16 @@ struct StagePool {
     std::vector<DevBuf<uint8_t>*> idle_planes;     // byte-map planes (one buffer per build in flight)
     std::vector<DevBuf<uint8_t>*> idle_tables;     // min_count counting tables (one per build that uses the cutoff)
     int device = -1;
+    // the counting table the last batch with a cutoff was counted in, for cobs_gpu_last_count_table (diagnostics):
+    // its buffer, slots and text bytes as BuildContext::clear_table set them; forgotten when the idle buffers are freed
+    DevBuf<uint8_t>* last_table = nullptr;
+    uint64_t last_cap = 0, last_total = 0;
+    void note_table(DevBuf<uint8_t>* b, uint64_t cap, uint64_t total) {
+        std::lock_guard<std::mutex> g(mu);
+        last_table = b;
+        last_cap = cap;
+        last_total = total;
+    }
     void drop_idle() {                             // mu held
         for (Stage* s : idle) delete s;
         idle.clear();
@@ -110,6 +120,8 @@ struct StagePool {
         idle_planes.clear();
         for (auto* b : idle_tables) delete b;
         idle_tables.clear();
+        last_table = nullptr;
+        last_cap = last_total = 0;
     }
     DevBuf<uint8_t>* take_table(int dev) {
         std::lock_guard<std::mutex> g(mu);

@@ -63,6 +63,16 @@ cobs_gpu_status cobs_gpu_page_columns(const cobs_gpu_index* ix, size_t file_no, 
 cobs_gpu_status cobs_gpu_read_rows(const cobs_gpu_index* ix, size_t file_no, uint32_t page,
                                    uint64_t row0, uint64_t nrows, uint8_t* out, size_t out_pitch);
 
+/* ---- the counting table of a build with min_count ------------------------- */
+/* The open-addressing table the LAST batch of the last build with min_count >= 2 was counted in (abundance_kernels.hpp),
+ * read back from the current device: out[0] = its slots (a power of two, 0 = there is no table: no such build yet, the
+ * buffers released by cobs_gpu_build_release_buffers, or another device current), out[1] = the text bytes of that batch.
+ * owner[slot] = 0 (free) or tag << 40 | (batch offset of the term's first occurrence + 1), count[slot] = its occurrences,
+ * saturating at min_count.  Either array may be NULL; both NULL asks for out alone; cap_slots < out[0] is
+ * COBS_GPU_ERR_CAPACITY with out filled in.  Host code only (a copy from the buffer the stage pool keeps); not to be called
+ * while a build is running.  Tests read it to see which slots known keys took. */
+cobs_gpu_status cobs_gpu_last_count_table(uint64_t out[2], uint64_t* owner, uint32_t* count, size_t cap_slots);
+
 /* ---- bookkeeping ---------------------------------------------------------- */
 /* Per-launch bookkeeping of the last cobs_gpu_batch_run (for rooflines):
  * out[0] = algorithmic bytes of the scan kernel(s): sum over queries of
